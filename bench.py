@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- ringGroth16 prover throughput on MI355X (BASELINE.json metric, headline configuration).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the headline line (metric, value, ms_per_step, ...).
+--full adds the legs beyond that figure, each untimed and after the K steps: measured peaks, the per-kernel
+profile and rooflines, the standalone NTT and dyadic legs, the post-run oracle check, the C3F leg, the other BASELINE
+configurations and the CPU baseline (N > 1: the transport phases and the sharded oracle check).  --dump-outputs DIR writes
+the proof of the last timed step as DIR/proof.npy (float64; every residue < 2^53, so the values are exact).
 
 One step = one groth16::prover call (zk_proof_systems/groth16/groth16.tcc:70-115: the witness map and
 all encoding inner products) of the HEADLINE statement: m = 2^16 constraints on the ring N = 8192,
@@ -416,6 +422,15 @@ def cpu_baseline(prm, m, n_aux):
     }
 
 
+def dump_outputs(out_dir, proof):
+    """--dump-outputs: the proof the last timed step returned ([3, L, 2, K, N_enc] residues, 6 MiB at the headline) as
+    out_dir/proof.npy in float64.  Every residue is below its modulus < 2^53, so the conversion is exact."""
+    words = proof.detach().cpu().numpy()
+    assert words.min() >= 0 and words.max() < 2**53, "proof residues out of range"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "proof.npy"), words.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -432,6 +447,11 @@ def main():
     ap.add_argument("--no-friendly-primes", "--no-recipe-primes", dest="no_friendly_primes", action="store_true",
                     help="skip the second leg on preset C3F (ring primes = 1 mod 2^20: complete transforms)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short Rinocchio legs at the shapes of BASELINE configs[3] / configs[4]")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure (peaks, per-kernel rooflines, NTT / dyadic legs, oracle check, "
+                         "C3F, other configurations, CPU baseline; N > 1: transport phases and check); the --no-* options apply to these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the proof of the last timed step as DIR/proof.npy (float64, exact)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -470,7 +490,7 @@ def main():
     t_s = time.perf_counter()
     dev = Device(prm_local, local_rank)
     setup["context_ms"] = round((time.perf_counter() - t_s) * 1e3, 1)  # rs_ctx_create: transform tables of every prime, index map
-    if world == 1:
+    if world == 1 and args.full:
         try:
             MEASURED.update(dev.measure_peaks())
         except Exception as e:  # e.g. the two 2 GiB buffers do not fit: the line then carries no measured denominators
@@ -554,6 +574,8 @@ def main():
         elapsed = float(tt.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = m * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proof[0])
     setup["first_proof_ms"] = round(first_ms, 1)
     setup["first_proof_extra_ms"] = round(first_ms - ms_per_step, 1)
     setup["note"] = ("not in the timed region: context creation, R1CS upload, and what the first proof of a (context, m) pays once -- witness-map "
@@ -562,7 +584,7 @@ def main():
     # ---- N > 1: one more (untimed) step with the collectives bracketed by HIP events on the streams they run on: what each
     # transport phase moved and how long it took on this rank, and the device time of the rank's own kernels
     transport_phases = None
-    if world > 1:
+    if world > 1 and args.full:
         RD.STATS.reset(True)
         dev.set_profiling(True)
         dev.profile_read()
@@ -586,7 +608,7 @@ def main():
     # (tests/dist_check.py): no multi-GPU run has been measured by any round, so a bench line from one must say that the
     # transport it timed also carries a correct proof (the headline-size proof itself is checked at N = 1)
     transport_check = None
-    if world > 1 and not args.no_check:
+    if world > 1 and args.full and not args.no_check:
         from tests.dist_check import sharded_proof_matches_oracle
         t_s = time.perf_counter()
         tc_preset, tc_m = ("toyC3" if prm.L == 4 else "toy"), 12
@@ -598,7 +620,7 @@ def main():
 
     # ---- per-kernel device time of one more (untimed) step: HIP events on the launch stream inside the library
     roofline = mac_roofline = timings = kernels = None
-    if world == 1:
+    if world == 1 and args.full:
         stale = {}
         pmc, stale["traffic"] = load_pmc("traffic", prm.name, m)
         fp64_pmc, stale["fp64"] = load_pmc("fp64", prm.name, m)
@@ -620,7 +642,7 @@ def main():
 
     # ---- the standalone transform (row a4), HBM bound by design: 16 bytes per coefficient per transform, on 4 GiB
     ntt_roofline = None
-    if world == 1 and not args.no_ntt:
+    if world == 1 and args.full and not args.no_ntt:
         from ringsnark_amd import _lib
         reps, blocks = 10, 5
 
@@ -677,7 +699,7 @@ def main():
 
     # ---- rows a2 / a8 of SURVEY 8(d) and the reference's micro-timings: dyadic ring ops, enc_add, encode / decode
     dyadic = None
-    if world == 1 and not args.no_ntt:
+    if world == 1 and args.full and not args.no_ntt:
         try:
             dyadic = dyadic_leg(dev, prm)
             p60 = P.preset("micro60")  # microbench.cpp:13-14,33-36: N = 16384, {59, 60, 60}-bit primes -- the integer (Montgomery) arithmetic
@@ -690,14 +712,14 @@ def main():
 
     # ---- untimed post-run check of the timed proof against the CPU oracle
     check = None
-    if world == 1 and not args.no_check:
+    if world == 1 and args.full and not args.no_check:
         pk.clear()  # the check releases the key (pk1 holds the last references) before it re-runs the witness map
         ok, info = post_run_check(dev, prm, cs, dcs, asg, pk1, proof[0], m, window1 or pk1["s_pows"].shape[0], n_slabs=3)
         check = dict(info, ok=ok)
 
     # ---- the same statement on "friendly" ring primes (preset C3F: = 1 mod 2^20, complete transforms; the headline of rounds 1-5), one GPU
     friendly = None
-    if world == 1 and prm.name == "C3" and not args.no_friendly_primes:
+    if world == 1 and args.full and prm.name == "C3" and not args.no_friendly_primes:
         del proof[0]
         proof.append(None)
         pk.clear()
@@ -769,7 +791,7 @@ def main():
             out["friendly_primes"] = friendly
         if other is not None:
             out["other_configs"] = other
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(prm, m, n_aux)
         print(json.dumps(out), flush=True)
     bad = (check is not None and not check["ok"]) or (friendly is not None and "check" in friendly and not friendly["check"]["ok"])

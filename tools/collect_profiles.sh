@@ -28,9 +28,9 @@ run_pass() {  # run_pass <name> <expected csv glob> <command...>
     echo "collect_profiles: pass $name wrote no $want" >&2; FAILED=1
   fi
 }
-PROBE="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-check --no-ntt --no-recipe-primes --no-other-configs --preset $PRESET"  # exactly 3 proofs: warm-up, timed, profiled
+PROBE="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-check --no-ntt --no-recipe-primes --no-other-configs --preset $PRESET"  # exactly 3 proofs: warm-up, timed, profiled
 if [[ $STAGES == *k* ]]; then
-  run_pass bench_stats "stats/*kernel_stats.csv" rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-check --no-recipe-primes --no-other-configs --preset "$PRESET"
+  run_pass bench_stats "stats/*kernel_stats.csv" rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-check --no-recipe-primes --no-other-configs --preset "$PRESET"
 fi
 if [[ $STAGES == *p* ]]; then
   run_pass pmc_mix "pmc_mix/*counter_collection.csv" rocprofv3 --kernel-trace --output-format csv -d "$OUT/pmc_mix" -o run \
