@@ -3,6 +3,7 @@
 The library is the product: there is no CPU fallback.  Importing this module without the built
 shared object raises, and every entry point raises RsError on a non-zero status.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -121,6 +122,11 @@ SIGNATURES = {
     "rs_chain_assignment": (C.c_int, [vp, vp, C.c_size_t, vp]),
 }
 
+TUNING_SIGNATURES = {  # every function of include/ringsnark_amd/tuning.h
+    "rs_get_tuning": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
+    "rs_tuning_key": (C.c_char_p, [C.c_int]),
+}
+
 _lib = None
 
 
@@ -134,7 +140,7 @@ def load():
             "ringsnark_amd/librs_hip.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
             "the HIP library is the only implementation, there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -147,15 +153,53 @@ def check(status):
         raise RsError(status, load().rs_last_error().decode("utf-8", "replace"))
 
 
+# ---- tuning knobs (csrc/tuning.hpp): process-wide, every accepted value gives identical results ----
+def set_tuning(key, value):
+    check(load().rs_set_tuning(key.encode(), int(value)))
+
+
+def get_tuning(key):
+    v = C.c_int()
+    check(load().rs_get_tuning(key.encode(), C.byref(v)))
+    return v.value
+
+
+def tuning_keys():
+    keys = []
+    while (k := load().rs_tuning_key(len(keys))) is not None:
+        keys.append(k.decode())
+    return keys
+
+
+@contextlib.contextmanager
+def tuning(**knobs):
+    """Scoped override: sets the named knobs in argument order and, on exit (normal or not), writes the values they had
+    back in reverse order.  If a set raises, the knobs set before it are restored before the error propagates."""
+    with contextlib.ExitStack() as stack:
+        for key, value in knobs.items():
+            saved = get_tuning(key)
+            set_tuning(key, value)
+            stack.callback(set_tuning, key, saved)
+        yield
+
+
+def tuning_from_env(name="RS_TUNING"):
+    """Sets the knobs listed as `key=value,key=value` in the environment variable `name` (developer tools).
+    Empty entries are skipped; an entry without `=` or with an unknown key raises."""
+    for kv in filter(None, os.environ.get(name, "").split(",")):
+        set_tuning(*kv.split("="))
+
+
 def source_hash():
     """sha256 (first 16 hex digits) over the sources the device library is built from: ringsnark_amd/csrc/*.{hip,hpp},
-    csrc/Makefile and include/ringsnark_amd.h.  profiles/*_pmc_*.json carry it, so that bench.py can tell whether a
+    csrc/Makefile, include/ringsnark_amd.h and include/ringsnark_amd/tuning.h.  profiles/*_pmc_*.json carry it, so that bench.py can tell whether a
     committed counter file was collected on the kernels it is running (round-3 verdict: nothing tied the two)."""
     import glob
     import hashlib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     files = sorted(glob.glob(os.path.join(root, "ringsnark_amd", "csrc", "*.hip")) + glob.glob(os.path.join(root, "ringsnark_amd", "csrc", "*.hpp")))
-    files += [os.path.join(root, "ringsnark_amd", "csrc", "Makefile"), os.path.join(root, "include", "ringsnark_amd.h")]
+    files += [os.path.join(root, "ringsnark_amd", "csrc", "Makefile"), os.path.join(root, "include", "ringsnark_amd.h"),
+              os.path.join(root, "include", "ringsnark_amd", "tuning.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode())

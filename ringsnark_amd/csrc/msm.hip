@@ -113,18 +113,17 @@ static void launch_mac(rs_ctx *ctx, const MacArgs &a, const MsmScratch &sc, hipS
   RS_HIP(hipGetLastError());
 }
 
-extern int g_mac_variant, g_mac_ablate, g_plain_variant, g_mac_chunk_units, g_mac_share_keys;
 static void launch_mac_v2(rs_ctx *ctx, const MacArgs2 &a, const MsmScratch &sc, hipStream_t st) {
   const size_t lds = (padded_len((size_t)ctx->N_enc) + (size_t)ctx->N_enc) * sizeof(double);
   const int rows = a.n_chunks * ctx->L;
   const unsigned blocks = (unsigned)(((rows + 7) / 8) * 8 * ctx->K);
-  if (g_mac_variant == 3 && ctx->logN_enc == 13) {  // 16 waves of 128 VGPRs (4 waves per SIMD), plaintext row not prefetched
+  if (g_tune.mac_variant == 3 && ctx->logN_enc == 13) {  // 16 waves of 128 VGPRs (4 waves per SIMD), plaintext row not prefetched
     set_max_dyn_lds((const void *)mac_kernel_v2<1024, 13>, (int)lds);
     hipLaunchKernelGGL((mac_kernel_v2<1024, 13>), dim3(blocks), dim3(1024), lds, st, a, ctx->L, ctx->K, ctx->logN_enc, sc.coeff<Mod>());
     RS_HIP(hipGetLastError());
     return;
   }
-  if (ctx->logN_enc == 13 && g_mac_variant != 4) {
+  if (ctx->logN_enc == 13 && g_tune.mac_variant != 4) {
 #define RS_MAC_LAUNCH(AB)                                                                                             \
   do {                                                                                                                \
     set_max_dyn_lds((const void *)mac_kernel_v2<512, 13, AB>, \
@@ -133,7 +132,7 @@ static void launch_mac_v2(rs_ctx *ctx, const MacArgs2 &a, const MsmScratch &sc, 
                        ctx->logN_enc, sc.coeff<Mod>());                                                               \
   } while (0)
 #ifdef RS_EXPERIMENTS  // timing-only ablations (wrong results): never part of the release library
-    switch (g_mac_ablate) {
+    switch (g_tune.mac_ablate) {
       case 1: RS_MAC_LAUNCH(1); break;
       case 2: RS_MAC_LAUNCH(2); break;
       case 6: RS_MAC_LAUNCH(6); break;
@@ -232,15 +231,6 @@ __global__ void __launch_bounds__(256) broadcast_rows_kernel(const uint64_t *__r
 }
 void batch_encode_run(rs_ctx *ctx, const uint64_t *d_rings, uint64_t *d_plain, size_t count, hipStream_t st);
 
-int g_mac_ablate = 0;
-int g_mac_ct_temporal = 0;  // tuning knob "mac_ct_temporal": mac_kernel_v3 reads the ciphertext words with temporal loads (A/B: does the second group's read of a shared key vector find them in L2 more often?)
-int g_mac_share_keys = 1;  // tuning knob "mac_share_keys": two key vectors share the plaintext spectrum (mac_kernel_v4; 8192 and 16384 points)
-int g_msm_host_tile = 1024;  // tuning knob "msm_host_tile": terms per staging buffer of a host-resident key
-int g_msm_c_mib = 2048;       // tuning knob "msm_c_mib": workspace of the centred plaintext rows of one term tile
-int g_mac_chunk_units = 768;  // tuning knob "mac_chunk_units": (limb, prime, chunk) units per MAC launch (term chunks = units / (L K))
-int g_plain_variant = 1;  // 1: plain_center_wide_kernel at N_enc = 8192; 0: plain_center_kernel
-int g_mac_variant = 5;  // 6: as 5, one-key launches at N_enc = 8192 in the 512-thread shape (mac_kernel_v4<13, ., 1>: four waves per SIMD); 5: half-spectrum wide kernel at N_enc = 8192 (else as 3); 3: streaming kernel, 1024-thread shape at N_enc = 8192 (else as 2); 2: 512-thread streaming kernel; 1: generic kernel
-
 // Core grouped MSM.  addends: optional per-output (n_crs * n_groups) device pointers to encoding
 // elements added to the result (pk.alpha / pk.beta of groth16.tcc:95,103).
 // crs_window != 0: every CRS vector is stored as `crs_window` consecutive elements and logical
@@ -286,7 +276,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   // the plaintext of (1, ..., 1); the wide 8192-point kernel has no such path: there the rows are expanded into a workspace.
   bool any_sc = false;
   for (int v = 0; v < n_vecs; v++) any_sc = any_sc || vecs[v].slot_const;
-  const bool sc_native = !(std::is_same<M, Mod>::value && g_plain_variant == 1 && n == 8192 && (ctx->N == 8192 || ctx->N == 4096));
+  const bool sc_native = !(std::is_same<M, Mod>::value && g_tune.plain_variant == 1 && n == 8192 && (ctx->N == 8192 || ctx->N == 4096));
   std::vector<const uint64_t *> coeff_ptr(n_vecs);
   for (int v = 0; v < n_vecs; v++) coeff_ptr[v] = vecs[v].d_coeff;
   if (any_sc && sc_native && !sc.d_ones_plain) {
@@ -350,7 +340,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   const int n_sets = n_crs * n_groups;
   // tiling: C workspace <= ~2 GiB (knob msm_c_mib)
   const size_t c_bytes_per_term = (size_t)n_groups * L * n * sizeof(double);
-  size_t tile_terms = std::max<size_t>(1, std::min<size_t>(Tmax, ((size_t)g_msm_c_mib << 20) / c_bytes_per_term));
+  size_t tile_terms = std::max<size_t>(1, std::min<size_t>(Tmax, ((size_t)g_tune.msm_c_mib << 20) / c_bytes_per_term));
   if (crs_window) {
     size_t p2 = 1;
     while (p2 * 2 <= tile_terms) p2 *= 2;
@@ -363,7 +353,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   uint64_t *stage = nullptr;
   size_t stage_words = 0;
   if (crs_on_host) {
-    tile_terms = std::min<size_t>(tile_terms, (size_t)std::max(1, g_msm_host_tile));
+    tile_terms = std::min<size_t>(tile_terms, (size_t)std::max(1, g_tune.msm_host_tile));
     if (crs_window) {
       size_t p2 = 1;
       while (p2 * 2 <= tile_terms) p2 *= 2;
@@ -410,8 +400,8 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   };
   // mac_kernel_v4 (two key vectors) runs ONE workgroup per CU: half the workgroup slots, half the chunks (measured at the
   // configs[3] shape: 111 -> 106 ms)
-  const int chunk_units = (n_crs == 2 && g_mac_share_keys && g_mac_variant >= 5 && (n == 8192 || n == 16384)) ? (g_mac_chunk_units + 1) / 2
-                                                                                                              : g_mac_chunk_units;
+  const int chunk_units = (n_crs == 2 && g_tune.mac_share_keys && g_tune.mac_variant >= 5 && (n == 8192 || n == 16384)) ? (g_tune.mac_chunk_units + 1) / 2
+                                                                                                              : g_tune.mac_chunk_units;
   int n_chunks = (int)std::min<size_t>(tile_terms, (size_t)std::max(1, (chunk_units + L * K - 1) / (L * K)));
   {  // the (chunk, limb) rows of a launch are dealt to the 8 XCDs: a row count that is not a multiple of 8 leaves slots idle
     int step = 8;
@@ -430,8 +420,8 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   (void)plain13;
   bool v3 = false, plain_wide = false, hybrid = false;
   if constexpr (FP) {
-    v3 = g_mac_variant >= 5 && (n == 8192 || n == 16384);  // 6: one-key launches in the 512-thread shape (mac_kernel_v4<13, ., 1>)
-    plain_wide = g_plain_variant == 1 && n == 8192 && (ctx->N == 8192 || ctx->N == 4096);
+    v3 = g_tune.mac_variant >= 5 && (n == 8192 || n == 16384);  // 6: one-key launches in the 512-thread shape (mac_kernel_v4<13, ., 1>)
+    plain_wide = g_tune.plain_variant == 1 && n == 8192 && (ctx->N == 8192 || ctx->N == 4096);
   } else {
     // Hybrid context: ring primes beyond 2^50 (SEAL's 54-bit BFVDefault(2048) prime of the reference's logistic-regression
     // benchmark) on the integer arithmetic, data primes below 2^50: the plaintext row is produced by the integer kernel and
@@ -440,7 +430,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     for (int i = 0; i < L; i++) maxq = std::max(maxq, ctx->q[i]);
     int max_vecs = 1;
     for (int g = 0; g < n_groups; g++) max_vecs = std::max(max_vecs, pa.g[g].n);
-    hybrid = ctx->hybrid && g_mac_variant >= 5 && (n == 8192 || n == 16384) &&
+    hybrid = ctx->hybrid && g_tune.mac_variant >= 5 && (n == 8192 || n == 16384) &&
              (double)max_vecs * (0.5 * (double)maxq + 1.0) < 9007199254740992.0;
     v3 = hybrid;
   }
@@ -559,15 +549,15 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     };
     // streaming kernel, one accumulator set (CRS vector c, group g) per launch.  With two CRS
     // vectors (Rinocchio's s_pows / alpha_s_pows) the plaintext transform is repeated per vector:
-    // measured faster than the generic kernel that shares it (g_mac_variant == 2: generic for n_crs == 2).
-    const bool v2 = FP && g_mac_variant >= 2 && (n_crs == 1 || g_mac_variant != 2) && n >= 2048 && n <= 8192;
+    // measured faster than the generic kernel that shares it (g_tune.mac_variant == 2: generic for n_crs == 2).
+    const bool v2 = FP && g_tune.mac_variant >= 2 && (n_crs == 1 || g_tune.mac_variant != 2) && n >= 2048 && n <= 8192;
     if (v3) {
       {
         // bound of a plaintext row: the sum of the centred lifts of the group's vectors
         uint64_t maxq = 0;
         for (int i = 0; i < L; i++) maxq = std::max(maxq, ctx->q[i]);
         const double b0 = 0.5 * (double)maxq * MAX_GROUP_VECS + (double)MAX_GROUP_VECS;
-        if (n_crs == 2 && g_mac_share_keys) {
+        if (n_crs == 2 && g_tune.mac_share_keys) {
           // Rinocchio's ten inner products (rinocchio.tcc:106-160): every vector against both key vectors, one transform
           for (int g0 = 0; g0 < n_groups; g0 += RS_MAC4_GROUPS) {
             const int ng = std::min(RS_MAC4_GROUPS, n_groups - g0);
@@ -599,7 +589,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
                            terms * L * K * (ntt_fp64(nd, logn_d) + 8.0 * nd / 2.0 + 2.0 * 15.0 * nd));
             launch_mac_v4(ctx, a4, paired, sc, st);
           }
-        } else if (g_mac_variant == 6 && n == 8192) {
+        } else if (g_tune.mac_variant == 6 && n == 8192) {
           // one key vector per launch in the 512-thread shape of mac_kernel_v4 (four waves per SIMD), two groups that read it
           // as neighbouring workgroups of an XCD (A and B against s_pows, groth16.tcc:89-103)
           for (int c = 0; c < n_crs; c++)
@@ -651,7 +641,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
             a3.part_stride = (size_t)n_sets * enc_words;
             a3.n_groups = ng;
             a3.paired = paired;
-            a3.ct_temporal = g_mac_ct_temporal;
+            a3.ct_temporal = g_tune.mac_ct_temporal;
             a3.n_chunks = base.n_chunks;
             a3.terms_per_chunk = base.terms_per_chunk;
             a3.accumulate = base.accumulate;
@@ -688,7 +678,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
         // every ciphertext word of the group's terms once, every plaintext row once (shared by the K
         // prime workgroups through L2), the accumulator set written once
         const double terms = (double)a2.terms;
-        ProfScope prof(ctx, st, (g_mac_variant == 3 && ctx->logN_enc == 13) ? "mac_kernel_v2<1024, 13, 0>" : "mac_kernel_v2", terms * ((double)enc_words * 8.0 + (double)L * nd * 8.0) + (double)enc_words * 8.0,
+        ProfScope prof(ctx, st, (g_tune.mac_variant == 3 && ctx->logN_enc == 13) ? "mac_kernel_v2<1024, 13, 0>" : "mac_kernel_v2", terms * ((double)enc_words * 8.0 + (double)L * nd * 8.0) + (double)enc_words * 8.0,
                        terms * L * K * (ntt_fp64(nd, logn_d) + 15.0 * nd));
         launch_mac_v2(ctx, a2, sc, st);
       }
@@ -751,7 +741,7 @@ void msm_run(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_le
 }
 // can a call with linear-form vectors be served? (FP64 context on the wide plaintext kernel)
 bool msm_supports_lin(const rs_ctx *ctx) {
-  return !ctx->use_int && g_plain_variant == 1 && ctx->N_enc == 8192 && (ctx->N == 8192 || ctx->N == 4096);
+  return !ctx->use_int && g_tune.plain_variant == 1 && ctx->N_enc == 8192 && (ctx->N == 8192 || ctx->N == 4096);
 }
 void batch_encode_run(rs_ctx *ctx, const uint64_t *d_rings, uint64_t *d_plain, size_t count, hipStream_t st) {
   if (!count) return;

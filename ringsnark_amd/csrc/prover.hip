@@ -19,8 +19,6 @@ void witness_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_asg, const ui
                  bool compact = false, const size_t (*rows)[2] = nullptr);
 void msm_scratch_release(rs_ctx *ctx);
 
-int g_prover_lin_io = 1;  // tuning knob "prover_lin_io": io vectors of groth16::prover as linear forms (MsmLin)
-
 __global__ void __launch_bounds__(256) fill_ones_kernel(uint64_t *p, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 1;
@@ -119,7 +117,7 @@ int rs_groth16_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *
   // The io vectors are linear forms of the primary inputs (witness.hip): when the inner product can take them in that
   // form (MsmLin) they are neither written by the witness map nor read and transformed by the inner product.
   const size_t nk = cs->n_inputs + 1;  // [1, x_1 .. x_n_inputs]; their encodings are staged in the (then unused) io rows
-  const bool lin = g_prover_lin_io && msm_supports_lin(ctx) && witness_io_shortcut(cs) &&
+  const bool lin = g_tune.prover_lin_io && msm_supports_lin(ctx) && witness_io_shortcut(cs) &&
                    nk * std::max<size_t>(rw, (size_t)ctx->L * ctx->N_enc) <= m * rw;
   uint64_t *outs[7] = {lin ? nullptr : A_io, lin ? nullptr : B_io, nullptr, A_mid, B_mid, nullptr, H};
   witness_run(ctx, cs, d_assignment, nullptr, nullptr, nullptr, outs, nullptr, st);

@@ -241,7 +241,6 @@ __global__ void __launch_bounds__(THREADS) ntt_kernel(uint64_t *__restrict__ dat
 // Wave-private variant (ntt_core.hpp "wp"): one cross-wave round, then every wave finishes its own
 // contiguous block without workgroup barriers, and moves it between LDS and global memory itself
 // with fully coalesced 16-byte accesses.
-int g_ntt_repeat = 1;
 // Break chip-wide lockstep: every workgroup of a launch runs the same load -> compute -> store
 // sequence, so without help all of them hit HBM at the same time and then all leave it idle.
 // The first generation of workgroups starts after a pseudo-random delay of up to `units` x ~1.7 us;
@@ -306,7 +305,7 @@ static void launch_ntt_wp(const NttTable &t, uint64_t *d_data, size_t batch, hip
   auto kern = ntt_kernel_wp<INV, MAXR, THREADS, MINW>;
   set_max_dyn_lds((const void *)kern, (int)lds);
   hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(THREADS), lds, st, d_data, t.logn, logw, INV ? t.d_itw : t.d_tw,
-                     t.mod, t.ninv, INV ? t.inv_red_mask : t.fwd_red_mask, g_ntt_repeat);
+                     t.mod, t.ninv, INV ? t.inv_red_mask : t.fwd_red_mask, g_tune.ntt_repeat);
   RS_HIP(hipGetLastError());
 }
 
@@ -460,11 +459,10 @@ __global__ void __launch_bounds__(1024) ntt_io_kernel(uint64_t *__restrict__ dat
   else
     lds_ntt_fwd_io<4>(s, gin, gout, logn, logn, tw, 1, mod, 0u);
 }
-int g_int_ntt_variant = 1;  // tuning knob "int_ntt_variant": 1 = ntt_io_kernel (lengths >= 2^10), 0 = ntt_generic_kernel
 void launch_ntt_int(rs_ctx *ctx, const NttTableI &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st) {
   (void)ctx;
   if (batch == 0) return;
-  if (g_int_ntt_variant == 1 && t.logn >= 10) {  // at least two rounds, so that the in-place global reads all precede the writes
+  if (g_tune.int_ntt_variant == 1 && t.logn >= 10) {  // at least two rounds, so that the in-place global reads all precede the writes
     const size_t lds = padded_len((size_t)1 << t.logn) * sizeof(uint64_t);
     const int thr = std::max(64, std::min(1024, (1 << t.logn) >> 4));
     if (inverse) {
@@ -489,9 +487,6 @@ void launch_ntt_int(rs_ctx *ctx, const NttTableI &t, uint64_t *d_data, size_t ba
   RS_HIP(hipGetLastError());
 }
 
-bool g_force_int = false;  // tuning knob "force_int_arith" (tests: both arithmetics on the same primes)
-int g_ntt_variant = 14;  // tuning knob (rs_set_tuning("ntt_variant", v)): see launch_ntt
-
 template <bool INV, int MAXR, bool DIN, bool DOUT, int THREADS>
 static void launch_ntt_variant(const NttTable &t, uint64_t *d_data, size_t batch, hipStream_t st) {
   const size_t lds = padded_len((size_t)1 << t.logn) * sizeof(double);
@@ -505,13 +500,12 @@ static void launch_ntt_variant(const NttTable &t, uint64_t *d_data, size_t batch
 }
 
 // ntt_wide.hpp kernels: persistent, two workgroups of 256 threads per CU (16384 points: one of 512)
-int g_ntt_wide_grid = 256;  // tuning knob "ntt_wide_grid": CUs to fill (workgroups = this x what fits one CU)
 template <int LOGN, bool RED>
 static void launch_ntt_wide_shape(const NttTable &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st) {
   using S = WideShape<LOGN>;
   const int lds = (int)S::LDS_BYTES;
   const size_t per_cu = std::min<size_t>(8 / (S::T / 64), (size_t)(160 * 1024) / S::LDS_BYTES);  // 2 waves per SIMD
-  const unsigned grid = (unsigned)std::min<size_t>(batch, (size_t)g_ntt_wide_grid * per_cu);
+  const unsigned grid = (unsigned)std::min<size_t>(batch, (size_t)g_tune.ntt_wide_grid * per_cu);
   if (inverse) {
     auto kern = ntt_inv_wide_kernel<LOGN, RED>;
     set_max_dyn_lds((const void *)kern, lds);
@@ -547,8 +541,8 @@ void launch_ntt(rs_ctx *ctx, const NttTable &t, uint64_t *d_data, size_t batch, 
     else                                                                               \
       launch_ntt_variant<false, MAXR, DIN_F, DOUT_F, THR>(t, d_data, batch, st);       \
     break;
-  if (g_ntt_variant == 14 && launch_ntt_wide(t, d_data, batch, inverse, st)) return;
-  if ((g_ntt_variant == 12 || g_ntt_variant == 14) && !inverse && t.logn >= 12 && t.logn <= 13 && t.fwd_red_mask < 4) {
+  if (g_tune.ntt_variant == 14 && launch_ntt_wide(t, d_data, batch, inverse, st)) return;
+  if ((g_tune.ntt_variant == 12 || g_tune.ntt_variant == 14) && !inverse && t.logn >= 12 && t.logn <= 13 && t.fwd_red_mask < 4) {
     const size_t lds = (padded_len((size_t)1 << t.logn) + ((size_t)1 << t.logn)) * sizeof(double);
     const unsigned grid = (unsigned)std::min<size_t>(batch, 256);
     if (t.logn == 13) {
@@ -563,10 +557,10 @@ void launch_ntt(rs_ctx *ctx, const NttTable &t, uint64_t *d_data, size_t batch, 
     RS_HIP(hipGetLastError());
     return;
   }
-  const int wp_waves = (g_ntt_variant == 9 || g_ntt_variant == 13) ? 16 : (g_ntt_variant == 10 ? 4 : 8);
+  const int wp_waves = (g_tune.ntt_variant == 9 || g_tune.ntt_variant == 13) ? 16 : (g_tune.ntt_variant == 10 ? 4 : 8);
   const bool wp_ok = (1 << t.logn) >= wp_waves * LDS_BLOCK_MIN;  // wave-private blocks need n / W >= LDS_BLOCK_MIN
-  if (wp_ok && g_ntt_variant >= 8 && g_ntt_variant <= 14) {
-    switch (g_ntt_variant) {
+  if (wp_ok && g_tune.ntt_variant >= 8 && g_tune.ntt_variant <= 14) {
+    switch (g_tune.ntt_variant) {
       case 8:
       case 12:  // streaming forward kernel not applicable (inverse, or shape): wave-private kernel
       case 14:  // wide kernels not applicable (shape)
@@ -587,7 +581,7 @@ void launch_ntt(rs_ctx *ctx, const NttTable &t, uint64_t *d_data, size_t batch, 
     }
     return;
   }
-  switch (g_ntt_variant) {
+  switch (g_tune.ntt_variant) {
     RS_NTT_CASE(1, 4, false, false, false, false, 512)
     RS_NTT_CASE(2, 4, true, false, false, true, 512)
     RS_NTT_CASE(3, 4, true, true, true, true, 512)
@@ -755,6 +749,39 @@ __global__ void __launch_bounds__(256) ring_nonzero_kernel(const uint64_t *__res
   if (__syncthreads_or(nz) && threadIdx.x == 0) flags[blockIdx.x] = 1u;
 }
 
+// ---- tuning knobs (tuning.hpp) ----------------------------------------------------------------
+Tuning g_tune;
+namespace {
+struct TuneKnob {
+  const char *name;
+  int Tuning::*member;
+  TuneRule rule;
+  int lo, hi;
+  const char *reject;
+};
+#define RS_TUNING_ROW(name, def, rule, lo, hi, reject, doc) {#name, &Tuning::name, TuneRule::rule, lo, hi, reject},
+const TuneKnob g_tune_knobs[] = {
+    RS_TUNING_KNOBS(RS_TUNING_ROW)
+#ifdef RS_EXPERIMENTS
+    RS_TUNING_KNOBS_EXPERIMENTS(RS_TUNING_ROW)
+#endif
+};
+#undef RS_TUNING_ROW
+const TuneKnob &tune_knob(const char *key) {
+  RS_REQUIRE(key, "null argument");
+  for (const TuneKnob &k : g_tune_knobs)
+    if (!strcmp(k.name, key)) return k;
+  throw Error(RS_ERR_INVALID, std::string("unknown tuning key ") + key);
+}
+void tune_check_force_bc(int value) { RS_REQUIRE(value == 0 || (value >= 5 && value <= 20), "witness_force_bc must be 0 or in [5, 20]"); }
+void tune_check_sub_ct(int value) {
+  (void)value;
+#ifndef RS_EXPERIMENTS  // the superseded A/B variants 1 (sub_ntt_ct_kernel) and 3 (sub_ntt_wide16_kernel) are not compiled in
+  if (value != 0 && value != 2) throw Error(RS_ERR_UNSUPPORTED, "witness_sub_ct 1 and 3 exist in the experiments build only");
+#endif
+}
+}  // namespace
+
 }  // namespace rs
 
 using namespace rs;
@@ -797,7 +824,7 @@ int rs_ctx_create(int device, int N, int L, const uint64_t *q, int N_enc, int K,
   c->K = K;
   c->logN_enc = 0;
   while ((1 << c->logN_enc) < N_enc) c->logN_enc++;
-  c->use_int = any_big || g_force_int;
+  c->use_int = any_big || g_tune.force_int_arith;
   for (int i = 0; i < L; i++) c->q[i] = q[i];
   for (int j = 0; j < K; j++) c->Q[j] = Q[j];
   if (c->use_int) {
@@ -816,7 +843,7 @@ int rs_ctx_create(int device, int N, int L, const uint64_t *q, int N_enc, int K,
     RS_HIP(hipMemcpy(c->d_Qmod_i, Qm.data(), sizeof(ModI) * K, hipMemcpyHostToDevice));
     // Hybrid: only ring primes are beyond 2^50 (the 54-bit BFVDefault(2048) prime of bench_logistic_regression_inference.cpp
     // :20-27 under 48/49-bit data primes): the inner products -- everything mod Q_j -- keep the FP64 kernels (msm.hip)
-    bool small_Q = !g_force_int;
+    bool small_Q = !g_tune.force_int_arith;
     for (int j = 0; j < K; j++) small_Q = small_Q && Q[j] < (1ull << 50);
     for (int i = 0; i < L; i++) small_Q = small_Q && q[i] < (1ull << 54);
     c->hybrid = small_Q;
@@ -1015,92 +1042,26 @@ int rs_ring_is_zero(rs_ctx *ctx, const uint64_t *d_a, size_t count, uint8_t *h_f
 
 int rs_set_tuning(const char *key, int value) {
   RS_API_BEGIN
-  RS_REQUIRE(key, "null argument");
-  if (std::string(key) == "ntt_variant")
-    g_ntt_variant = value;
-  else if (std::string(key) == "force_int_arith")  // contexts created from now on use the Montgomery path regardless of prime size
-    g_force_int = value != 0;
-#ifdef RS_EXPERIMENTS  // these two CHANGE THE RESULTS (timing experiments, tools/): `make experiments` only
-  else if (std::string(key) == "ntt_repeat")
-    g_ntt_repeat = value;
-  else if (std::string(key) == "mac_ablate")
-    g_mac_ablate = value;
-#endif
-  else if (std::string(key) == "mac_variant")
-    g_mac_variant = value;
-  else if (std::string(key) == "mac_ct_temporal")
-    g_mac_ct_temporal = value ? 1 : 0;
-  else if (std::string(key) == "plain_variant")
-    g_plain_variant = value;
-  else if (std::string(key) == "prover_lin_io")
-    g_prover_lin_io = value;
-  else if (std::string(key) == "msm_host_tile")
-    g_msm_host_tile = std::max(1, value);
-  else if (std::string(key) == "msm_c_mib") {
-    RS_REQUIRE(value >= 1, "msm_c_mib must be positive");
-    g_msm_c_mib = value;
-  } else if (std::string(key) == "mac_chunk_units")
-    g_mac_chunk_units = std::max(1, value);
-  else if (std::string(key) == "mac_share_keys")
-    g_mac_share_keys = value != 0;
-  else if (std::string(key) == "ntt_wide_grid")
-    g_ntt_wide_grid = std::max(1, value);
-  else if (std::string(key) == "int_ntt_variant")
-    g_int_ntt_variant = value;
-  else if (std::string(key) == "witness_sub_log") {
-    RS_REQUIRE(value == 12 || value == 13, "witness_sub_log must be 12 or 13");
-    g_witness_sub_log = value;
-  } else if (std::string(key) == "witness_h_coset") {
-    g_witness_h_coset = value ? 1 : 0;
-  } else if (std::string(key) == "witness_sub12_cross") {
-    RS_REQUIRE(value >= 1 && value <= 8, "witness_sub12_cross must be in [1, 8]");
-    g_witness_sub12_cross = value;
-  } else if (std::string(key) == "witness_cross_pair")
-    g_witness_cross_pair = value ? 1 : 0;
-  else if (std::string(key) == "witness_cross_maxr") {
-    RS_REQUIRE(value >= 1 && value <= 6, "witness_cross_maxr must be in [1, 6]");
-    g_witness_cross_maxr = value;
-  } else if (std::string(key) == "witness_force_bc") {
-    RS_REQUIRE(value == 0 || (value >= 5 && value <= 20), "witness_force_bc must be 0 or in [5, 20]");
-    g_witness_force_bc = value;  // takes effect for plans built afterwards (plans are cached per context and size)
-  } else if (std::string(key) == "witness_bc2") {
-    g_witness_bc2 = value ? 1 : 0;  // takes effect for plans built afterwards, like witness_force_bc
-  } else if (std::string(key) == "witness_inc") {
-    g_witness_inc = value ? 1 : 0;  // incomplete transforms instead of block convolutions; plans built afterwards
-  } else if (std::string(key) == "witness_tree_log") {
-    RS_REQUIRE(value == 13 || value == 14, "witness_tree_log must be 13 or 14");
-    g_witness_tree_log = value;
-  } else if (std::string(key) == "witness_sub_ct") {
-#ifndef RS_EXPERIMENTS
-    // 0: generic kernel, 2: sub_ntt_wide_kernel (default).  The superseded A/B variants 1 (sub_ntt_ct_kernel) and 3
-    // (sub_ntt_wide16_kernel) are compiled into the experiments build only (make -C ringsnark_amd/csrc experiments)
-    if (value != 0 && value != 2) throw Error(RS_ERR_UNSUPPORTED, "witness_sub_ct 1 and 3 exist in the experiments build only");
-#endif
-    g_witness_sub_ct = value;
+  const TuneKnob &k = tune_knob(key);
+  switch (k.rule) {
+    case TuneRule::ANY: break;
+    case TuneRule::BOOL: value = value ? 1 : 0; break;
+    case TuneRule::MIN1: value = std::max(1, value); break;
+    case TuneRule::RANGE: RS_REQUIRE(value >= k.lo && value <= k.hi, std::string(k.name) + " " + k.reject); break;
+    case TuneRule::FORCE_BC: tune_check_force_bc(value); break;
+    case TuneRule::SUB_CT: tune_check_sub_ct(value); break;
   }
-  else if (std::string(key) == "witness_tree_ct")
-    g_witness_tree_ct = value;
-  else if (std::string(key) == "witness_tree_fwd")
-    g_witness_tree_fwd = value ? 1 : 0;
-  else if (std::string(key) == "witness_level_turn")
-    g_witness_level_turn = value ? 1 : 0;
-  else if (std::string(key) == "witness_h_turn")
-    g_witness_h_turn = value ? 1 : 0;
-  else if (std::string(key) == "witness_tree_once")
-    g_witness_tree_once = value ? 1 : 0;
-  else if (std::string(key) == "witness_big_ws_mib") {
-    RS_REQUIRE(value >= 64, "witness_big_ws_mib must be at least 64");
-    g_witness_big_ws_mib = value;
-  } else if (std::string(key) == "witness_col_budget_mib") {
-    RS_REQUIRE(value >= 1, "witness_col_budget_mib must be positive");
-    g_witness_col_budget_mib = value;
-  } else if (std::string(key) == "witness_lds_logM") {
-    RS_REQUIRE(value >= 6 && value <= 13, "witness_lds_logM must be in [6, 13]");
-    g_witness_lds_logM = value;
-  }
-  else
-    throw Error(RS_ERR_INVALID, std::string("unknown tuning key ") + key);
+  g_tune.*k.member = value;
   RS_API_END
+}
+int rs_get_tuning(const char *key, int *value) {
+  RS_API_BEGIN
+  RS_REQUIRE(value, "null argument");
+  *value = g_tune.*tune_knob(key).member;
+  RS_API_END
+}
+const char *rs_tuning_key(int index) {
+  return index >= 0 && index < (int)std::size(g_tune_knobs) ? g_tune_knobs[index].name : nullptr;
 }
 
 int rs_set_profiling(rs_ctx *ctx, int enabled) {

@@ -11,8 +11,10 @@
 #include <vector>
 
 #include "../../include/ringsnark_amd.h"
+#include "../../include/ringsnark_amd/tuning.h"
 #include "intmod.hpp"
 #include "host_math.hpp"
+#include "tuning.hpp"
 
 namespace rs {
 
@@ -182,7 +184,7 @@ struct rs_ctx {
   int noise_tb = 0;
   void *d_crt_limbs = nullptr;
   std::mutex mu;
-  std::map<size_t, rs::WitnessPlan *> plans;  // keyed by padded domain size M
+  std::map<std::pair<size_t, uint64_t>, rs::WitnessPlan *> plans;  // keyed by (m, plan_knob_sig()), witness.hip get_plan
   // workspace cache (grown on demand, per context; calls that need workspace serialise on mu)
   rs::DeviceBuf ws[16];
   hipStream_t cur_stream = nullptr;  // stream of the call that holds mu (rs::WsScope)
@@ -291,27 +293,6 @@ inline hipStream_t S(rs_stream s) { return (hipStream_t)s; }
 
 // launch helpers implemented in the .hip files
 void msm_scratch_release(rs_ctx *ctx);  // msm.hip
-extern int g_mac_variant, g_mac_ablate, g_plain_variant, g_mac_chunk_units, g_msm_host_tile, g_mac_share_keys, g_msm_c_mib;  // msm.hip tuning knobs
-extern int g_witness_h_coset;               // witness.hip: coset form of H when C is interpolated
-extern int g_witness_sub12_cross;           // witness.hip: most cross stages of a transform run on 2^12 blocks
-extern int g_witness_sub_log;              // witness.hip: block (log2) of the rooted sub-transforms, 13 or 12
-extern int g_witness_cross_pair;           // witness.hip: paired groups / 16-byte accesses in the cross passes
-extern int g_witness_cross_maxr;           // witness.hip: stages per cross pass of the multi-pass transforms
-extern int g_witness_force_bc;             // witness.hip: cap on the transform length (block-convolution path)
-extern int g_witness_bc2;                  // witness.hip: two-dimensional block convolutions where they apply
-extern int g_mac_ct_temporal;             // msm.hip: mac_kernel_v3 reads ciphertext words with temporal loads
-extern int g_witness_inc;                  // witness.hip: incomplete transforms (witness_inc.hpp) where they apply, instead of block convolutions
-extern int g_prover_lin_io;               // prover.hip: io vectors as linear forms in groth16::prover
-extern int g_witness_tree_log;            // witness.hip: tile of the wide product-tree kernel (13 or 14)
-extern int g_witness_sub_ct;              // witness.hip: compile-time-length sub-transform kernel
-extern int g_witness_tree_ct;             // witness.hip: level-unrolled product-tree kernel
-extern int g_witness_tree_fwd;             // witness.hip: forward cross stages of level 15 inside the tile kernel
-extern int g_witness_level_turn;           // witness.hip: the turn between two tree levels as one pass (cross_level_turn_kernel)
-extern int g_witness_h_turn;               // witness.hip: the turn of H as one pass (cross_turn_kernel)
-extern int g_witness_tree_once;            // witness.hip: product-tree tiles in one launch per chunk
-extern int g_witness_big_ws_mib;           // witness.hip: workspaces of one multi-pass sub-chunk of columns
-extern int g_witness_col_budget_mib;       // witness.hip: column workspace of one chunk of the witness map
-extern int g_witness_lds_logM;           // witness.hip: largest column (log2) handled inside one LDS tile
 void launch_ntt(rs_ctx *ctx, const NttTable &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st);
 void launch_ntt_int(rs_ctx *ctx, const NttTableI &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st);
 }  // namespace rs

@@ -88,7 +88,6 @@ struct WitnessPlan {
   // Some ring prime lacks a 2M-th root of unity and the columns take the multi-pass path with INCOMPLETE transforms
   // (witness_inc.hpp; LimbPlan::adic per prime) instead of block convolutions: bcLog = 0, the full-length launch sequences run.
   bool incomplete = false;
-  uint64_t knob_sig = 0;  // plan_knob_sig() when the plan was built: get_plan rebuilds when a knob it depends on has changed
   std::vector<LimbPlan> limb;
   // coefficients_for_Z of every limb as the compact [m + 1][L] device array the inner products take a slot-constant
   // vector in (rs_msm_vec::slot_const): a per-(context, m) constant, uploaded once (witness_Z_rows)
@@ -260,23 +259,11 @@ static uint64_t plain_word(const rs_ctx *ctx, uint64_t v, uint64_t p) {
   return ctx->use_int ? word_of(HostArith<ModI>::plain(v, p)) : word_of(HostArith<Mod>::plain(v, p));
 }
 
-int g_witness_h_coset = 1;      // tuning knob "witness_h_coset": H on a coset (four length-M transforms) when the call interpolates C; 0: always big_h
-int g_witness_sub_log = 12;     // tuning knob "witness_sub_log": 12 = rooted sub-transforms on blocks of 2^12 (sub_ntt_w12_kernel) where sub_block_log says so; 13: never
-int g_witness_sub12_cross = 4;  // tuning knob "witness_sub12_cross": most cross stages of a transform that takes 2^12 blocks
-int g_witness_cross_pair = 1;  // tuning knob "witness_cross_pair": two groups per thread and 16-byte accesses in the cross passes (0: the round-3 form)
-int g_witness_cross_maxr = 6;  // tuning knob "witness_cross_maxr": most stages of one cross pass (FP64 arithmetic; 4 = the round-3 passes)
-int g_witness_force_bc = 0;  // tuning knob "witness_force_bc": pretend the ring primes have only this 2-adicity (tests)
-int g_witness_bc2 = 1;       // tuning knob "witness_bc2": two-dimensional block convolutions where they apply (0: the pairwise form)
-
-// tuning knob "witness_inc": ring primes without a 2M-th root of unity run the multi-pass path on INCOMPLETE transforms
-// (witness_inc.hpp) where the conditions of build_plan hold; 0: the block convolutions (round 3's path for those primes)
-int g_witness_inc = 1;
-extern int g_witness_lds_logM, g_witness_tree_log, g_witness_tree_ct;
 static bool single_tile_ok(int logM);
 // largest tile of the product tree in the multi-pass path: full transforms of that length run inside the tile kernels
 static int tree_tile_log(bool fp, int logM) {
-  const int logT = std::min(g_witness_lds_logM, logM);
-  return (fp && logT == 13 && logM >= 15 && g_witness_tree_ct == 2 && g_witness_tree_log >= 14) ? 14 : logT;
+  const int logT = std::min(g_tune.witness_lds_logM, logM);
+  return (fp && logT == 13 && logM >= 15 && g_tune.witness_tree_ct == 2 && g_tune.witness_tree_log >= 14) ? 14 : logT;
 }
 
 static void free_plan_tables(WitnessPlan *P);
@@ -294,17 +281,17 @@ static WitnessPlan *build_plan(rs_ctx *ctx, size_t m) {
   P->limb.resize(ctx->L);
   int vmin = 64;
   for (int li = 0; li < ctx->L; li++) vmin = std::min(vmin, host::two_adicity(ctx->q[li]));
-  if (g_witness_force_bc > 0) vmin = std::min(vmin, g_witness_force_bc);  // tests: the block path on well-endowed primes
+  if (g_tune.witness_force_bc > 0) vmin = std::min(vmin, g_tune.witness_force_bc);  // tests: the block path on well-endowed primes
   const bool blocked = vmin < logM + 1;
   // Incomplete transforms (witness_inc.hpp): the multi-pass path as it is, every transform longer than 2^(a prime's
   // 2-adicity) stopped that many stages early.  Needs: columns that take the multi-pass path; full transforms inside the
   // product tree's tiles; at most RS_INC_MAX stages missing, all of them inside the LAST round of a sub-transform block.
   {
-    const int logT = std::min(g_witness_lds_logM, logM);
+    const int logT = std::min(g_tune.witness_lds_logM, logM);
     // (M = 2^14 on the FP64 arithmetic normally runs in ONE 2^14 tile -- single_tile_ok -- whose Newton conversion needs a
     // complete 2^15-point transform: a prime without it takes the multi-pass path on 2^13 tiles instead, one stage short)
-    const bool multi = logM > g_witness_lds_logM;
-    P->incomplete = blocked && g_witness_inc && multi && vmin >= tree_tile_log(!ctx->use_int, logM) && logM + 1 - vmin <= RS_INC_MAX &&
+    const bool multi = logM > g_tune.witness_lds_logM;
+    P->incomplete = blocked && g_tune.witness_inc && multi && vmin >= tree_tile_log(!ctx->use_int, logM) && logM + 1 - vmin <= RS_INC_MAX &&
                     std::min(logT, 12) > RS_INC_MAX;
   }
   const bool bcpath = blocked && !P->incomplete;
@@ -313,7 +300,7 @@ static WitnessPlan *build_plan(rs_ctx *ctx, size_t m) {
   if (bcpath && logM > 20)
     throw Error(RS_ERR_UNSUPPORTED, "witness map beyond 2^20 constraints needs ring primes = 1 mod 2^(log2 M - 3) (full-length transforms, "
                                     "at most four stages short); the block convolutions of other primes stop at 2^20");
-  P->bc2 = bcpath && g_witness_bc2 && !ctx->use_int && vmin >= 14 && logM >= 15;
+  P->bc2 = bcpath && g_tune.witness_bc2 && !ctx->use_int && vmin >= 14 && logM >= 15;
   P->bcLog = bcpath ? (P->bc2 ? 14 : std::min(vmin, 13)) : 0;
   // every context prime is 1 mod 2*N_enc with N_enc >= 16, so the 2-adicity is at least 5
   RS_REQUIRE(!bcpath || P->bcLog > SCHOOL_LEVELS, "ring prime with too little 2-adicity for the witness map");
@@ -330,7 +317,7 @@ static WitnessPlan *build_plan(rs_ctx *ctx, size_t m) {
     lp.adic = 64;
     if (P->incomplete) {
       int a = host::two_adicity(p);
-      if (g_witness_force_bc > 0) a = std::min(a, g_witness_force_bc);
+      if (g_tune.witness_force_bc > 0) a = std::min(a, g_tune.witness_force_bc);
       if (a < logM + 1) lp.adic = a;
     }
     const int tabLog = bcpath ? P->bcLog : std::min(logM + 1, lp.adic);
@@ -610,27 +597,19 @@ static void free_plan(WitnessPlan *P) {
 // the knobs build_plan's choice of path (full length / incomplete / block convolutions) and table forms depend on
 static uint64_t plan_knob_sig() {
   uint64_t h = 1469598103934665603ull;
-  for (int v : {g_witness_lds_logM, g_witness_tree_log, g_witness_tree_ct, g_witness_inc, g_witness_bc2, g_witness_force_bc})
+  for (int v : {g_tune.witness_lds_logM, g_tune.witness_tree_log, g_tune.witness_tree_ct, g_tune.witness_inc, g_tune.witness_bc2, g_tune.witness_force_bc})
     h = (h ^ (uint64_t)(uint32_t)v) * 1099511628211ull;
   return h;
 }
+// Plans are cached per (m, plan_knob_sig()) and live until rs_witness_plans_destroy: a plan is never freed under a call
+// that holds its tables, and no lookup synchronises.  Cost: a context on which plan-shaping knobs are flipped (tests and
+// tools/ only; the product never changes a knob) keeps one plan per distinct signature it has seen.
 WitnessPlan *get_plan(rs_ctx *ctx, size_t m) {
-  const uint64_t sig = plan_knob_sig();
-  auto it = ctx->plans.find(m);
-  if (it != ctx->plans.end()) {
-    if (it->second->knob_sig == sig) return it->second;
-    // a tuning knob changed since the plan was built (tests, A/B tools): its tables may be in another form -- rebuild
-    RS_HIP(hipDeviceSynchronize());
-    free_plan(it->second);
-    ctx->plans.erase(it);
-  }
-  WitnessPlan *P = build_plan(ctx, m);
-  P->knob_sig = sig;
-  ctx->plans[m] = P;
-  return P;
+  const std::pair<size_t, uint64_t> key{m, plan_knob_sig()};
+  auto it = ctx->plans.find(key);
+  if (it != ctx->plans.end()) return it->second;
+  return ctx->plans[key] = build_plan(ctx, m);
 }
-
-
 
 // Z as the provers hand it to the inner products: [m + 1][L] values on the device, built at first use (one blocking
 // upload per plan; every later proof reads the cached array -- no host transpose, no synchronisation inside a proof)
@@ -692,11 +671,6 @@ static ColPlansT<M> make_colplans(rs_ctx *ctx, const WitnessPlan *P, int limb0 =
 
 static int col_threads(size_t M) { return (int)std::max<size_t>(64, std::min<size_t>(1024, M / 8)); }
 
-int g_witness_lds_logM = 13;  // columns up to 2^13 run entirely inside one LDS tile
-int g_witness_tree_log = 14;  // largest tile of the wide product-tree kernel: 13 or 14 (tuning knob "witness_tree_log")
-int g_witness_tree_ct = 2;    // 2: wide product-tree kernel (tree_wide_kernel) for 2^13 tiles; 1: level-unrolled tree_columns_kernel; 0: level loop
-int g_witness_sub_ct = 2;     // 1: compile-time-length sub-transform kernel for 2^13 blocks of the multi-pass path
-
 // Newton -> monomial levels 1..logT on tiles of 2^logT coefficients of [ncols][M] columns; with
 // `newton` (logT == logM) the tiles hold values and the Newton conversion runs first, in the same launch
 // FP64 instructions (per lane) of the product tree on one tile of T = 2^logT coefficients: levels
@@ -711,7 +685,7 @@ static double tree_fp64(double T, int logT, bool pw_reduce = true) {
 }
 // Wout / rf (2^14 tiles of the wide kernel only): the right tiles also run the rf forward cross stages of level 15 and write
 // that level's workspace [ncols][2^logM] (tree_wide_kernel<14, RF>); the caller then skips the level's source pass.
-static bool wide_ok_for_fwd(int logT, int rf) { return g_witness_tree_ct == 2 && logT == 14 && (rf == 2 || rf == 3); }
+static bool wide_ok_for_fwd(int logT, int rf) { return g_tune.witness_tree_ct == 2 && logT == 14 && (rf == 2 || rf == 3); }
 static void launch_tree_tiles(rs_ctx *ctx, double *cols, size_t ncols, size_t col0, int logM, int logT, size_t S,
                               size_t slots_per_limb, const ColPlans &cp, hipStream_t st, bool newton = false, double *Wout = nullptr, int rf = 0) {
   const size_t T = (size_t)1 << logT;
@@ -719,8 +693,8 @@ static void launch_tree_tiles(rs_ctx *ctx, double *cols, size_t ncols, size_t co
   // Newton conversion (single-tile columns): two passes of forward + inverse M-point transforms and two pointwise products
   const double newton_fp64 = newton ? 4.0 * ntt_fp64((double)T, logT) + 31.0 * (double)T : 0.0;
   // names as rocprofv3 prints them (a prefix of "rs::<name>") so that profiles/ and the live record can be joined
-  const bool ct13 = logT == 13 && g_witness_tree_ct;
-  const bool wide = !newton && g_witness_tree_ct == 2 && (logT == 13 || logT == 14);
+  const bool ct13 = logT == 13 && g_tune.witness_tree_ct;
+  const bool wide = !newton && g_tune.witness_tree_ct == 2 && (logT == 13 || logT == 14);
   RS_REQUIRE(!Wout || (wide_ok_for_fwd(logT, rf) && !newton), "tree tiles: forward stages of the next level need the wide 2^14 tile");
   const char *pname = wide ? (logT == 14 ? (Wout ? (rf == 3 ? "tree_wide_kernel<14, 3>" : "tree_wide_kernel<14, 2>") : "tree_wide_kernel<14, 0>") : "tree_wide_kernel<13, 0>")
                       : ct13 ? (newton ? "tree_columns_kernel<512, 13, true>" : "tree_columns_kernel<512, 13, false>")
@@ -766,7 +740,7 @@ static void launch_tree_tiles(rs_ctx *ctx, double *cols, size_t ncols, size_t co
       hipLaunchKernelGGL((tree_wide_kernel<13, 0>), dim3(grid), dim3(256), wl, st, cols, logM, col0, (unsigned)S, (unsigned)slots_per_limb, cp,
                          (double *)nullptr);
     }
-  } else if (thr == 512 && logT == 13 && g_witness_tree_ct) {
+  } else if (thr == 512 && logT == 13 && g_tune.witness_tree_ct) {
     if (newton)
       RS_TREE_LAUNCH_K((tree_columns_kernel<512, 13, true>));
     else
@@ -864,12 +838,12 @@ static void launch_cross(rs_ctx *ctx, CrossArgs a, size_t ncols, int logB, const
   while (done < ncross) {
     // FP64: up to six stages per pass (64 strided elements per thread: the pass is HBM bound, the registers are idle) --
     // a transform with five or six cross stages (M = 2^17, 2^18) crosses the workspace once instead of twice
-    const int R = pick_radix(ncross - done, std::is_same<M, Mod>::value ? std::max(1, std::min(6, g_witness_cross_maxr)) : 4);
+    const int R = pick_radix(ncross - done, std::is_same<M, Mod>::value ? std::max(1, std::min(6, g_tune.witness_cross_maxr)) : 4);
     a.s0 = INV ? logB + done : done;
     const bool special = INV ? (done + R >= ncross) : (done == 0);
     // two adjacent groups per thread, 16-byte accesses (cross_kernel<..., 2>): needs wave-uniform twiddles for 128
     // consecutive groups (smallest gap >= 2^7) and 16-byte aligned columns
-    const bool paired = g_witness_cross_pair && R <= 5 && logB >= 8 && a.logM >= 2 &&
+    const bool paired = g_tune.witness_cross_pair && R <= 5 && logB >= 8 && a.logM >= 2 &&
                         (((uintptr_t)a.W | (uintptr_t)a.src | (uintptr_t)a.dst) & 15) == 0;
     const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>((groups >> R) / (paired ? 512 : 256), 1024));
     const dim3 grid(gx, (unsigned)ncols);
@@ -894,7 +868,7 @@ static void launch_cross(rs_ctx *ctx, CrossArgs a, size_t ncols, int logB, const
 // FORWARD pass from a source costs more than the smaller block saves (measured on the headline).
 template <class M>
 static int sub_block_log(int logT, int logsub) {
-  return (std::is_same<M, Mod>::value && g_witness_sub_log == 12 && logT == 13 && logsub - 12 <= g_witness_sub12_cross) ? 12 : logT;
+  return (std::is_same<M, Mod>::value && g_tune.witness_sub_log == 12 && logT == 13 && logsub - 12 <= g_tune.witness_sub12_cross) ? 12 : logT;
 }
 
 // FP64 instructions per coefficient of the pointwise step of a fused sub-transform: one modular product, or (incomplete
@@ -925,20 +899,20 @@ static void launch_sub_inc(rs_ctx *ctx, typename ArithOf<M>::T *X, size_t ncols,
       {"sub_ntt_w12_kernel<4, 0>", "", "", "", ""}};
   RS_REQUIRE(inc >= 0 && inc <= RS_INC_MAX && (inc == 0 || (MODE != 1 && MODE != 4)) && logB > inc, "internal: sub-transform launch out of range");
 #ifdef RS_EXPERIMENTS
-  const bool ct = FP && logB == 13 && MODE != 1 && g_witness_sub_ct && (MODE != 4 || g_witness_sub_ct == 2) && (inc == 0 || g_witness_sub_ct == 2);  // MODE 4: generic, wide and 2^12 kernels only
+  const bool ct = FP && logB == 13 && MODE != 1 && g_tune.witness_sub_ct && (MODE != 4 || g_tune.witness_sub_ct == 2) && (inc == 0 || g_tune.witness_sub_ct == 2);  // MODE 4: generic, wide and 2^12 kernels only
 #else
-  const bool ct = FP && logB == 13 && MODE != 1 && g_witness_sub_ct == 2;  // 0: the generic kernel; 1 and 3 exist in the experiments build only
+  const bool ct = FP && logB == 13 && MODE != 1 && g_tune.witness_sub_ct == 2;  // 0: the generic kernel; 1 and 3 exist in the experiments build only
 #endif
   const double Bn = (double)((size_t)1 << logB), blocks = (double)(ncols * bpc);
   static const char *const names_w16[5] = {"sub_ntt_wide16_kernel<0>", "sub_ntt_wide16_kernel<1>", "sub_ntt_wide16_kernel<2>", "sub_ntt_wide16_kernel<3>", "sub_ntt_wide16_kernel<4>"};
-  const bool w12 = FP && logB == 12 && MODE != 1 && g_witness_sub_log == 12;
-  ProfScope prof(ctx, st, w12 ? names_w12[MODE][inc] : ct ? (g_witness_sub_ct == 3 ? names_w16[MODE] : g_witness_sub_ct == 2 ? names_wide[MODE][inc] : names_ct[MODE]) : names[MODE], blocks * Bn * (MODE == 4 ? 32.0 : MODE == 3 ? 24.0 : 16.0),
+  const bool w12 = FP && logB == 12 && MODE != 1 && g_tune.witness_sub_log == 12;
+  ProfScope prof(ctx, st, w12 ? names_w12[MODE][inc] : ct ? (g_tune.witness_sub_ct == 3 ? names_w16[MODE] : g_tune.witness_sub_ct == 2 ? names_wide[MODE][inc] : names_ct[MODE]) : names[MODE], blocks * Bn * (MODE == 4 ? 32.0 : MODE == 3 ? 24.0 : 16.0),
                  blocks * ((MODE >= 2 ? 2.0 : 1.0) * ntt_fp64(Bn, logB - inc) + (MODE == 4 ? 24.0 * Bn : MODE >= 2 ? pointwise_fp64(inc) * Bn : 0.0)));
   static TabPtrs none{};
   const TabPtrs &tp = tabs ? *tabs : none;
   if constexpr (FP) {
     const unsigned long long nb = (unsigned long long)(ncols * bpc);
-    if (logB == 12 && MODE != 1 && g_witness_sub_log == 12) {
+    if (logB == 12 && MODE != 1 && g_tune.witness_sub_log == 12) {
       const int wl = 4352 * (int)sizeof(double);
 #define RS_W12_LAUNCH(INC)                                                                                                              \
   hipLaunchKernelGGL((sub_ntt_w12_kernel<MODE, INC>), dim3((unsigned)std::min<unsigned long long>(nb, 1024)), dim3(256), wl, st, X,     \
@@ -959,7 +933,7 @@ static void launch_sub_inc(rs_ctx *ctx, typename ArithOf<M>::T *X, size_t ncols,
       return;
     }
 #ifdef RS_EXPERIMENTS
-    if (logB == 13 && MODE != 1 && MODE != 4 && g_witness_sub_ct == 3 && inc == 0) {
+    if (logB == 13 && MODE != 1 && MODE != 4 && g_tune.witness_sub_ct == 3 && inc == 0) {
       const int wl = (int)(WideShape<13>::TILE * sizeof(double));
       set_max_dyn_lds((const void *)sub_ntt_wide16_kernel<MODE>, wl);
       hipLaunchKernelGGL((sub_ntt_wide16_kernel<MODE>), dim3((unsigned)std::min<unsigned long long>(nb, 512)), dim3(512), wl, st, X,
@@ -968,7 +942,7 @@ static void launch_sub_inc(rs_ctx *ctx, typename ArithOf<M>::T *X, size_t ncols,
       return;
     }
 #endif
-    if (logB == 13 && MODE != 1 && g_witness_sub_ct == 2) {
+    if (logB == 13 && MODE != 1 && g_tune.witness_sub_ct == 2) {
       const int wl = (int)(WideShape<13>::TILE * sizeof(double));
 #define RS_WIDE_LAUNCH(INC)                                                                                                             \
   do {                                                                                                                                  \
@@ -993,7 +967,7 @@ static void launch_sub_inc(rs_ctx *ctx, typename ArithOf<M>::T *X, size_t ncols,
       return;
     }
 #ifdef RS_EXPERIMENTS
-    if (logB == 13 && MODE != 1 && MODE != 4 && g_witness_sub_ct && inc == 0) {
+    if (logB == 13 && MODE != 1 && MODE != 4 && g_tune.witness_sub_ct && inc == 0) {
       set_max_dyn_lds((const void *)sub_ntt_ct_kernel<MODE, 13>, (int)lds);
       hipLaunchKernelGGL((sub_ntt_ct_kernel<MODE, 13>), dim3((unsigned)(ncols * bpc)), dim3(512), lds, st, X, logsub - logB, tp,
                          (unsigned)std::max<size_t>(1, tab_period), (unsigned)bpc, col0, (unsigned)S, (unsigned)spl, cp);
@@ -1111,7 +1085,6 @@ static void bc2_conv(rs_ctx *ctx, Bc2Args a, int logY, size_t ncols, const TabPt
   RS_HIP(hipGetLastError());
 }
 
-int g_witness_h_turn = 1;  // tuning knob "witness_h_turn": fuse the last inverse cross pass of A B with the first forward pass of rev(A B)
 // The turn of H as one pass (cross_turn_kernel): reads a.W (the product's workspace, sub-transformed), writes a.dst (the
 // workspace of T = rev(P) mod x^(m-1), cross stages done).  Returns false when the two transforms need more than one cross
 // pass each (the caller then runs the two passes).
@@ -1120,8 +1093,8 @@ static bool launch_cross_turn(rs_ctx *ctx, CrossArgs a, size_t ncols, int logB, 
   using CPS = ColPlansT<M>;
   constexpr bool FP = std::is_same<M, Mod>::value;
   const int R = a.logtot - logB;
-  const int maxr = FP ? std::max(1, std::min(6, g_witness_cross_maxr)) : 4;
-  if (!g_witness_h_turn || R < 1 || R > maxr || a.logsub != a.logtot || logB < 8) return false;
+  const int maxr = FP ? std::max(1, std::min(6, g_tune.witness_cross_maxr)) : 4;
+  if (!g_tune.witness_h_turn || R < 1 || R > maxr || a.logsub != a.logtot || logB < 8) return false;
   if ((((uintptr_t)a.W | (uintptr_t)a.dst) & 15) != 0) return false;
   // cross_turn_kernel indexes the product at i0 = 2m - 2 - j - c >= 0 and shifts by E - 1 - (i0 >> logB) >= 0: holds for
   // M = next_pow2(m) (2m - 2 >= M >= B, 2m - 2 < 2M = 2^logtot) -- enforced, not assumed (round-5 advice): else the two passes
@@ -1150,7 +1123,6 @@ static bool launch_cross_turn(rs_ctx *ctx, CrossArgs a, size_t ncols, int logB, 
   return true;
 }
 
-int g_witness_level_turn = 1;  // tuning knob "witness_level_turn": fuse the last inverse cross pass of tree level l with the first forward pass of level l + 1
 // The turn between tree levels l = a.l and l + 1 as one pass (cross_level_turn_kernel) on the workspace a.W and the columns
 // a.dst; false when the two levels differ in block size or need more than one cross pass each.
 template <class M>
@@ -1158,8 +1130,8 @@ static bool launch_level_turn(rs_ctx *ctx, CrossArgs a, size_t ncols, int logB, 
   using CPS = ColPlansT<M>;
   constexpr bool FP = std::is_same<M, Mod>::value;
   const int RL = a.l - logB;
-  const int maxr = FP ? std::max(1, std::min(6, g_witness_cross_maxr)) : 4;
-  if (!g_witness_level_turn || logB != logB_next || RL < 1 || RL + 1 > maxr || logB < 8 || a.l + 1 > a.logtot) return false;
+  const int maxr = FP ? std::max(1, std::min(6, g_tune.witness_cross_maxr)) : 4;
+  if (!g_tune.witness_level_turn || logB != logB_next || RL < 1 || RL + 1 > maxr || logB < 8 || a.l + 1 > a.logtot) return false;
   if ((((uintptr_t)a.W | (uintptr_t)a.dst) & 15) != 0) return false;
   const bool pair = RL <= 3;
   const size_t groups = (((size_t)1 << a.logtot) >> (a.l + 1)) * (((size_t)1 << logB) / (pair ? 2 : 1));
@@ -1185,16 +1157,15 @@ static bool launch_level_turn(rs_ctx *ctx, CrossArgs a, size_t ncols, int logB, 
   return true;
 }
 
-// tuning knob "witness_tree_fwd": the tile kernel runs the forward cross stages of the first level above the tiles.  OFF by
+// g_tune.witness_tree_fwd: the tile kernel runs the forward cross stages of the first level above the tiles.  OFF by
 // default -- measured (profiles/r05_knob_ab_tree_once.txt): it removes a 9.8 ms pass and costs the tile kernel 16 ms (176 ->
 // 192 ms per headline proof): one workgroup per CU has nothing to hide its epilogue's LDS reads and stores behind.
-int g_witness_tree_fwd = 0;
 // Can the wide 2^14 tile kernel run the forward cross stages of level 15 (2 or 3 of them: blocks of 2^13 / 2^12)?
 template <class M>
 static bool tree_fwd_stages(const WitnessPlan *P) {
   if constexpr (!std::is_same<M, Mod>::value) return false;
-  const int logM = P->logM, logT = std::min(g_witness_lds_logM, logM);
-  if (!g_witness_tree_fwd || !(logT == 13 && logM >= 15 && g_witness_tree_ct == 2 && g_witness_tree_log >= 14)) return false;
+  const int logM = P->logM, logT = std::min(g_tune.witness_lds_logM, logM);
+  if (!g_tune.witness_tree_fwd || !(logT == 13 && logM >= 15 && g_tune.witness_tree_ct == 2 && g_tune.witness_tree_log >= 14)) return false;
   const int rf = 15 - sub_block_log<M>(logT, 15);
   return rf == 2 || rf == 3;
 }
@@ -1209,7 +1180,7 @@ static void big_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &cp
                        size_t ncols, size_t col0, size_t S, size_t spl, int limb0, hipStream_t st, int phases = 7, bool tree_fwd = false) {
   using T = typename ArithOf<M>::T;
   constexpr bool FP = std::is_same<M, Mod>::value;
-  const int logM = P->logM, logT = std::min(g_witness_lds_logM, logM);
+  const int logM = P->logM, logT = std::min(g_tune.witness_lds_logM, logM);
   int logB = sub_block_log<M>(logT, logM + 1);  // block of the rooted sub-transforms
   const size_t Mlen = P->M;
   CrossArgs a{};
@@ -1234,7 +1205,7 @@ static void big_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &cp
   // product tree: levels <= logTree inside LDS tiles (the wide kernel takes 2^14 tiles: one multi-pass level less)
   int logTree = logT;
   if constexpr (FP) {
-    if (logT == 13 && logM >= 15 && g_witness_tree_ct == 2 && g_witness_tree_log >= 14) logTree = 14;
+    if (logT == 13 && logM >= 15 && g_tune.witness_tree_ct == 2 && g_tune.witness_tree_log >= 14) logTree = 14;
     const int rf = tree_fwd ? logTree + 1 - sub_block_log<M>(logT, logTree + 1) : 0;
     if (phases & 2) launch_tree_tiles(ctx, X, ncols, col0, logM, logTree, S, spl, cp, st, false, tree_fwd ? W : nullptr, rf);
   } else {
@@ -1269,7 +1240,7 @@ static void big_h(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &cp, con
                   const typename ArithOf<M>::T *B, typename ArithOf<M>::T *H, typename ArithOf<M>::T *W1, typename ArithOf<M>::T *W2,
                   size_t ncols, size_t col0, size_t S, size_t spl, const uint64_t *d1, const uint64_t *d2, const uint64_t *d3,
                   const ColMap &cm, int limb0, hipStream_t st) {
-  const int logM = P->logM, logB = sub_block_log<M>(std::min(g_witness_lds_logM, logM), logM + 1);
+  const int logM = P->logM, logB = sub_block_log<M>(std::min(g_tune.witness_lds_logM, logM), logM + 1);
   const size_t Mlen = P->M;
   CrossArgs a{};
   a.logM = logM;
@@ -1326,7 +1297,7 @@ static void big_h_coset(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &c
                         typename ArithOf<M>::T *W1, typename ArithOf<M>::T *W2, size_t ncols, size_t col0, size_t S, size_t spl,
                         const uint64_t *d1, const uint64_t *d2, const uint64_t *d3, const ColMap &cm, int limb0, hipStream_t st) {
   using T = typename ArithOf<M>::T;
-  const int logM = P->logM, logB = sub_block_log<M>(std::min(g_witness_lds_logM, logM), logM);
+  const int logM = P->logM, logB = sub_block_log<M>(std::min(g_tune.witness_lds_logM, logM), logM);
   const size_t Mlen = P->M;
   T *W3 = W1 + ncols * Mlen;  // the second half of the [ncols][2M] workspace
   CrossArgs a{};
@@ -1364,12 +1335,10 @@ static void big_h_coset(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &c
   RS_HIP(hipGetLastError());
 }
 
-int g_witness_tree_once = 1;  // tuning knob "witness_tree_once": the product tree's tiles in one launch per chunk of columns
-int g_witness_big_ws_mib = 6 * 1024;  // tuning knob "witness_big_ws_mib": the two [cols][2M] workspaces of a multi-pass sub-chunk
 static size_t big_chunk_cols(const WitnessPlan *P) {
   // two [cols][2M] workspaces within ~6 GiB
   const size_t per_col = 4 * P->M * sizeof(double);
-  return std::max<size_t>(1, ((size_t)g_witness_big_ws_mib << 20) / per_col);
+  return std::max<size_t>(1, ((size_t)g_tune.witness_big_ws_mib << 20) / per_col);
 }
 
 // Columns handled by the M-tile kernels (fused Newton + tree, h_tile): 2^10 .. 2^13 at two workgroups
@@ -1377,7 +1346,7 @@ static size_t big_chunk_cols(const WitnessPlan *P) {
 // natural setting -- one launch instead of the multi-pass path.
 static bool single_tile_ok(int logM) {
   if (logM < 10) return false;
-  return logM <= g_witness_lds_logM || (logM == 14 && g_witness_lds_logM == 13);
+  return logM <= g_tune.witness_lds_logM || (logM == 14 && g_tune.witness_lds_logM == 13);
 }
 
 // ---- block-convolution path: host side ---------------------------------------------------------------------
@@ -1411,7 +1380,7 @@ static void bc_conv(rs_ctx *ctx, BcArgs a, size_t ncols, size_t per_unit, const 
 
 // columns per chunk such that the block workspaces (spectra + pair products, up to ~8M words per column) stay within ~6 GiB
 static size_t bc_chunk_cols(const WitnessPlan *P) {
-  return std::max<size_t>(1, ((size_t)g_witness_big_ws_mib << 20) / ((P->bc2 ? 12 : 10) * P->M * sizeof(double)));
+  return std::max<size_t>(1, ((size_t)g_tune.witness_big_ws_mib << 20) / ((P->bc2 ? 12 : 10) * P->M * sizeof(double)));
 }
 
 template <class M>
@@ -1441,7 +1410,7 @@ static void bc_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &cp,
   if constexpr (std::is_same<M, Mod>::value) {
     // ... through the wide tile kernel where it exists (2^13 / 2^14 tiles: the recipe primes of the headline shape have
     // 2-adicity 14, so the whole 2^14 tile of tree_wide_kernel<14> is available to them)
-    if ((bc == 13 || bc == 14) && g_witness_tree_ct == 2 && (bc == 13 || g_witness_tree_log >= 14))
+    if ((bc == 13 || bc == 14) && g_tune.witness_tree_ct == 2 && (bc == 13 || g_tune.witness_tree_log >= 14))
       launch_tree_tiles(ctx, X, ncols, col0, logM, bc, S, spl, cp, st);
     else
       launch_tree_tiles_generic<M>(ctx, X, ncols, col0, logM, bc, S, spl, cp, st);
@@ -1540,9 +1509,9 @@ static void bc2_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlans &cp, do
   }
   // product tree: levels <= 14 inside LDS tiles, the levels above as block convolutions F_node = F_left + (x^h + d) * F_right
   if (phases & 2)
-    launch_tree_tiles(ctx, X, ncols, col0, logM, (g_witness_tree_ct == 2 && g_witness_tree_log >= 14) ? 14 : 13, S, spl, cp, st);
+    launch_tree_tiles(ctx, X, ncols, col0, logM, (g_tune.witness_tree_ct == 2 && g_tune.witness_tree_log >= 14) ? 14 : 13, S, spl, cp, st);
   if (!(phases & 4)) return;
-  const int first = (g_witness_tree_ct == 2 && g_witness_tree_log >= 14) ? 15 : 14;
+  const int first = (g_tune.witness_tree_ct == 2 && g_tune.witness_tree_log >= 14) ? 15 : 14;
   bool fwd_done = false;  // this level's transform across blocks was run by the previous level's turn
   for (int l = first; l <= logM; l++) {
     a.l = l;
@@ -1557,7 +1526,7 @@ static void bc2_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlans &cp, do
     // level l's inverse transform across blocks + sink and level l + 1's source + forward transform as one pass
     // (bc2_level_turn_kernel; one-level transforms: the parent has at most 32 blocks)
     const int logYc = l - BC2_LOGB;
-    const bool turn = g_witness_level_turn && logYc >= 2 && logYc <= 4 && (size_t)ncols * (size_t)(a.units / 2) <= 65535;
+    const bool turn = g_tune.witness_level_turn && logYc >= 2 && logYc <= 4 && (size_t)ncols * (size_t)(a.units / 2) <= 65535;
     bc2_conv<BS_RIGHT, BD_COMBINE, 2>(ctx, a, logYc, ncols, &tp, nullptr, cp, st, fwd_done, turn);
     fwd_done = turn;
     if (turn) {
@@ -1604,7 +1573,7 @@ static void bc2_h(rs_ctx *ctx, const WitnessPlan *P, const ColPlans &cp, const d
   // the turn of H (bc2_h_turn_kernel): the product's inverse transform across blocks and the forward one of its reversal as
   // one pass, the 2M-word product buffer neither written nor read (one-level transforms of at most 16 blocks: M <= 2^16)
   // (the turn kernel reverses around 2m - 2: needs B <= 2m - 2 < 2M, true for M = next_pow2(m) -- checked, as in launch_cross_turn)
-  const bool turn = g_witness_h_turn && logY >= 2 && logY <= 4 && 2 * (long long)P->m - 2 >= (long long)BC2_B &&
+  const bool turn = g_tune.witness_h_turn && logY >= 2 && logY <= 4 && 2 * (long long)P->m - 2 >= (long long)BC2_B &&
                     2 * (long long)P->m - 2 < ((long long)2 << logM);
   bc2_conv<BS_CENTER, BD_PLAIN_SCALED, 3>(ctx, a, logY, ncols, nullptr, WsA, cp, st, false, turn);
   if (turn) {
@@ -1641,7 +1610,7 @@ static void launch_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> 
   if (P->bcLog) {  // a ring prime without a 2M-th root of unity: block convolutions
     const size_t chunk = std::min(ncols, bc_chunk_cols(P));
     if constexpr (FP) {
-      if (P->bc2 && chunk < ncols && g_witness_tree_once) {  // the product tree's tiles in one launch (see the full-length path below)
+      if (P->bc2 && chunk < ncols && g_tune.witness_tree_once) {  // the product tree's tiles in one launch (see the full-length path below)
         for (size_t c0 = 0; c0 < ncols; c0 += chunk)
           bc2_interp(ctx, P, cp, cols + c0 * P->M, std::min(chunk, ncols - c0), c0, S, slots_per_limb, limb0, st, 1);
         bc2_interp(ctx, P, cp, cols, ncols, 0, S, slots_per_limb, limb0, st, 2);
@@ -1669,7 +1638,7 @@ static void launch_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> 
       return;
     }
   }
-  if (P->logM <= g_witness_lds_logM) {
+  if (P->logM <= g_tune.witness_lds_logM) {
     // the 2M convolution tile, or the product tree's tile + scratch when M is below the LDS block size
     const size_t lds = std::max(padded_len(2 * P->M), padded_len(tree_scratch_offset((int)P->M) + P->M)) * sizeof(double);
     set_max_dyn_lds((const void *)interp_columns_kernel<ColPlansT<M>>, (int)lds);
@@ -1684,8 +1653,8 @@ static void launch_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> 
   // the tile kernel also writes level 15's workspace for the right children ([ncols][M], for ALL the columns it covers)
   // when that fits beside everything else (24 GiB; a configs[3] rank is tight)
   const bool tfwd = tree_fwd_stages<M>(P) && ncols * P->M * sizeof(double) <= ((size_t)24 << 30);
-  T *W = (T *)ws_get(ctx, 12, std::max(chunk * 2 * P->M, (tfwd && chunk < ncols && g_witness_tree_once) ? ncols * P->M : 0) * sizeof(double));
-  if (chunk < ncols && g_witness_tree_once) {
+  T *W = (T *)ws_get(ctx, 12, std::max(chunk * 2 * P->M, (tfwd && chunk < ncols && g_tune.witness_tree_once) ? ncols * P->M : 0) * sizeof(double));
+  if (chunk < ncols && g_tune.witness_tree_once) {
     // the tiles of the product tree work in place on the columns: ONE launch over all of them between the sub-chunked
     // phases (tile kernels like long launches: 183.5 -> 176 ms per headline proof when every launch covers a whole chunk,
     // profiles/r05_knob_ab_big_ws.txt; the workspace-bound phases keep their 6 GiB sub-chunks, which they prefer)
@@ -1738,7 +1707,7 @@ static void launch_h(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &cp, 
                        d1, d2, d3, cm);                                                                              \
   } while (0)
       if (thr == 1024) RS_H_LAUNCH((h_tile_kernel<1024, 0>));
-      else if (thr == 512 && g_witness_tree_ct) RS_H_LAUNCH((h_tile_kernel<512, 13>));
+      else if (thr == 512 && g_tune.witness_tree_ct) RS_H_LAUNCH((h_tile_kernel<512, 13>));
       else if (thr == 512) RS_H_LAUNCH((h_tile_kernel<512, 0>));
       else if (thr == 256) RS_H_LAUNCH((h_tile_kernel<256, 0>));
       else if (thr == 128) RS_H_LAUNCH((h_tile_kernel<128, 0>));
@@ -1748,7 +1717,7 @@ static void launch_h(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &cp, 
       return;
     }
   }
-  if (P->logM <= g_witness_lds_logM) {
+  if (P->logM <= g_tune.witness_lds_logM) {
     const size_t lds = padded_len(2 * Mlen) * sizeof(double);
     set_max_dyn_lds((const void *)h_columns_kernel<ColPlansT<M>>, (int)lds);
     ProfScope prof(ctx, st, "h_columns_kernel", (double)S * (double)Mlen * 24.0,
@@ -1763,7 +1732,7 @@ static void launch_h(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &cp, 
   T *W2 = (T *)ws_get(ctx, 13, chunk * 2 * Mlen * sizeof(double));
   for (size_t c0 = 0; c0 < S; c0 += chunk) {
     const size_t nc = std::min(chunk, S - c0);
-    if (Cc && g_witness_h_coset && P->limb[cm.limb0].d_cos_z)
+    if (Cc && g_tune.witness_h_coset && P->limb[cm.limb0].d_cos_z)
       big_h_coset<M>(ctx, P, cp, A + c0 * Mlen, B + c0 * Mlen, Cc + c0 * Mlen, H + c0 * Mlen, W1, W2, nc, c0, S, spl, d1, d2, d3, cm, cm.limb0, st);
     else
       big_h<M>(ctx, P, cp, A + c0 * Mlen, B + c0 * Mlen, H + c0 * Mlen, W1, W2, nc, c0, S, spl, d1, d2, d3, cm, cm.limb0, st);
@@ -1845,8 +1814,6 @@ static void build_io_cache(rs_ctx *ctx, const rs_r1cs *cs, const WitnessPlan *P,
   mc->io_M = M;
   mc->io_built = true;
 }
-
-int g_witness_col_budget_mib = 16 * 1024;  // column workspace of one chunk (tuning knob "witness_col_budget_mib")
 
 // One chunk of the witness map: limbs [limb0, limb0 + nl), slots [cm.slot0, cm.slot0 + cm.ns) of each.
 template <class M_>
@@ -1972,7 +1939,7 @@ static void witness_chunk(rs_ctx *ctx, const rs_r1cs *cs, WitnessPlan *P, const 
 // Witness map driver.  outs[k] (k = A_io,B_io,C_io,A_mid,B_mid,C_mid,H) may be null.  Slots
 // [slot0, slot0 + nslots) of every limb are processed; `compact` selects the output layout
 // [t][L][nslots] (a slot-sharded rank) instead of the full [t][L][N].  The columns are
-// worked through in chunks whose column-major workspace stays within g_witness_col_budget_mib
+// worked through in chunks whose column-major workspace stays within g_tune.witness_col_budget_mib
 // (at m = 2^16 and the headline ring that is one limb at a time: 3 x 4 GiB instead of 7 x 16 GiB).
 template <class M_>
 static void witness_run_arith(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_asg, const uint64_t *d1, const uint64_t *d2,
@@ -2021,7 +1988,7 @@ static void witness_run_arith(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_
     nvec += needH;
   }
   const size_t budget_cols =
-      std::max<size_t>(64, ((size_t)g_witness_col_budget_mib << 20) / (std::max(1, nvec) * M * sizeof(double)));
+      std::max<size_t>(64, ((size_t)g_tune.witness_col_budget_mib << 20) / (std::max(1, nvec) * M * sizeof(double)));
   ColMap cm{0, nslots, slot0, ctx->N, L, compact ? nslots : ctx->N, compact ? slot0 : 0};
   if ((size_t)nslots <= budget_cols) {
     const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)L, budget_cols / (size_t)nslots));

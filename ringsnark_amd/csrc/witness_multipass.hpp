@@ -6,7 +6,7 @@
 namespace rs {
 
 // =============================================================================================
-// Multi-pass column transforms for M > 2^g_witness_lds_logM (a column no longer fits one LDS tile).
+// Multi-pass column transforms for M > 2^g_tune.witness_lds_logM (a column no longer fits one LDS tile).
 // A cyclic transform of length n = n1 * Bn over a column held in global memory is
 //     forward:  log2(n1) "cross" stages (gap >= Bn; twiddles depend on the block index only),
 //               then n1 independent length-Bn sub-transforms rooted at tree nodes n1 + b, in LDS;
@@ -768,7 +768,7 @@ sub_ntt_ct_kernel(double *__restrict__ X, int log_n1, TabPtrs tabs, unsigned tab
 
 #endif  // RS_EXPERIMENTS
 
-// sub_ntt_ct_kernel in the wide form of ntt_wide.hpp (g_witness_sub_ct == 2): 256 threads x 32 coefficients per block of
+// sub_ntt_ct_kernel in the wide form of ntt_wide.hpp (g_tune.witness_sub_ct == 2): 256 threads x 32 coefficients per block of
 // 2^13, persistent, two workgroups per CU.  Forward rounds (4, 5, 4 stages); round 3 leaves every thread with 16
 // CONSECUTIVE spectrum points per group, which is exactly the operand set of the inverse's first round, so the table
 // product and inverse stages 0..3 follow in registers: the fused forward-multiply-inverse exchanges the tile four
@@ -1206,7 +1206,7 @@ sub_ntt_w12_kernel(double *__restrict__ X, int log_n1, TabPtrs tabs, unsigned ta
 }
 
 #ifdef RS_EXPERIMENTS  // superseded A/B variant (witness_sub_ct = 3, measured 11 % slower): experiments build only
-// sub_ntt_wide_kernel at FOUR waves per SIMD (g_witness_sub_ct == 3): 512 threads x 16 coefficients per block of 2^13,
+// sub_ntt_wide_kernel at FOUR waves per SIMD (g_tune.witness_sub_ct == 3): 512 threads x 16 coefficients per block of 2^13,
 // <= 128 registers, two workgroups (16 waves) per CU.  Forward rounds of 4, 3 and 2 stages, then the same fused middle
 // as the 32-coefficient form on 16 consecutive points (forward stages 9..12, table product, inverse stages 0..3), then
 // the mirror image: six tile exchanges instead of four, twice the waves to hide them behind.  Same stages, reduction

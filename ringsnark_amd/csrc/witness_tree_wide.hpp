@@ -5,7 +5,7 @@
 namespace rs {
 
 // =============================================================================================
-// Product-tree levels 1..13 on a 2^13 tile in the wide form (g_witness_tree_ct == 2): 256 threads x 32 coefficients.
+// Product-tree levels 1..13 on a 2^13 tile in the wide form (g_tune.witness_tree_ct == 2): 256 threads x 32 coefficients.
 //
 // tree_columns_kernel gives a lane 16 coefficients spread over its wave's block, runs every level's transforms in
 // radix-8 LDS rounds (138 tile passes per tile) and spends 40 % of its VALU instructions on addresses and selects.

@@ -1,9 +1,12 @@
 """HIP path vs the CPU oracle, through the C ABI (librs_hip.so).  Bit-exact: every comparison is
 an integer array equality.  Needs a real MI355X: run with -m gpu."""
+import contextlib
+
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from ringsnark_amd import _lib
 from ringsnark_amd import params as P
 from ringsnark_amd import r1cs as R
 from tests import helpers as H
@@ -16,17 +19,11 @@ _DEV = {}
 def dev_for(name):
     """Device per preset.  "<preset>+int": the same preset on the integer (Montgomery) arithmetic, which contexts
     otherwise select only when a modulus is >= 2^50 (tuning knob force_int_arith, read at context creation)."""
-    from ringsnark_amd import _lib
     from ringsnark_amd.device import Device
     if name not in _DEV:
         base, force = (name[:-4], True) if name.endswith("+int") else (name, False)
-        if force:
-            _lib.check(_lib.load().rs_set_tuning(b"force_int_arith", 1))
-        try:
+        with _lib.tuning(**(dict(force_int_arith=1) if force else {})):
             _DEV[name] = Device(P.preset(base))
-        finally:
-            if force:
-                _lib.check(_lib.load().rs_set_tuning(b"force_int_arith", 0))
     return _DEV[name]
 
 
@@ -37,7 +34,6 @@ def host(t):
 
 @pytest.mark.parametrize("name", ["toy", "toy49", "C2", "C3", "C5s", "C4", "toy54", "toy60", "micro60", "C5", "toy+int", "toy49+int"])
 def test_ntt_matches_oracle(name):
-    from ringsnark_amd import _lib
     dev = dev_for(name)
     prm = dev.prm
     logn = prm.N_enc.bit_length() - 1
@@ -192,20 +188,14 @@ def test_quarter_spectrum_mac_at_16384_points(name):
         for k in range(3):
             vk = v[k] if k < 2 else v[2][:short]
             assert (got4[c, k] == ctx.inner_product(crs, vk, threads=0, window=8)[0]).all(), (c, k)
-    _set_tuning(b"mac_share_keys", 0)
-    try:
+    with _lib.tuning(mac_share_keys=0):
         dev.set_profiling(True)
         ref4, _ = dev.msm([dev.put(crs0), dev.put(crs1)], g2, 3, crs_len=T, window=8)
         names = {k["name"] for k in dev.profile_read()}
         dev.set_profiling(False)
-    finally:
-        _set_tuning(b"mac_share_keys", 1)
     assert not any(k.startswith("mac_kernel_v4") for k in names) and (host(ref4) == got4).all()
-    _set_tuning(b"mac_variant", 1)
-    try:
+    with _lib.tuning(mac_variant=1):
         ref, _ = dev.msm([dev.put(crs0)], groups, ng, crs_len=T, window=8)
-    finally:
-        _set_tuning(b"mac_variant", 5)
     assert (host(ref) == got).all()
     if name == "C5":  # a two-vector group on the 54-bit prime: refused by the hybrid path, served by the integer kernel
         dev.set_profiling(True)
@@ -251,11 +241,8 @@ def test_grouped_msm_with_vectors_of_different_lengths(name):
         assert used2 == lens and (got2[0] == got[0]).all()
         for g, (v, k) in enumerate(zip(vs, kinds)):
             assert (got2[1, g] == ctx.inner_product(crs1, v, k, threads=0, window=16)[0]).all(), g
-        _set_tuning(b"mac_share_keys", 0)
-        try:
+        with _lib.tuning(mac_share_keys=0):
             ref2, _ = dev.msm([dev.put(crs), dev.put(crs1)], groups, 3, crs_len=T, window=16)
-        finally:
-            _set_tuning(b"mac_share_keys", 1)
         assert (host(ref2) == got2).all()
 
 
@@ -266,7 +253,6 @@ def test_wide_kernels_equal_their_predecessors_and_the_oracle(name):
     one-limb-zero term, a Scalar-1 term and a short vector; one configuration also against the oracle.  C2 has
     N = 4096 < N_enc (slots beyond N stay zero), C3 N = N_enc."""
     import torch
-    from ringsnark_amd import _lib
     dev = dev_for(name)
     prm = dev.prm
     ctx = H.oracle_ctx(prm)
@@ -274,17 +260,14 @@ def test_wide_kernels_equal_their_predecessors_and_the_oracle(name):
     for modset, idx, q in ((_lib.RS_MOD_COEFF, prm.K - 1, prm.Q[-1]), (_lib.RS_MOD_PLAIN, 0, prm.q[0])):
         src = torch.empty((37, prm.N_enc), dtype=torch.int64, device=dev.device).random_(0, int(q))
         outs = []
-        try:
-            for v in (0, 12, 14):
-                _set_tuning(b"ntt_variant", v)
+        for v in (0, 12, 14):
+            with _lib.tuning(ntt_variant=v):
                 d = src.clone()
                 dev.ntt(d, modset, idx)
                 f = d.clone()
                 dev.ntt(d, modset, idx, inverse=True)
                 assert (d == src).all(), ("roundtrip", v)
                 outs.append(f)
-        finally:
-            _set_tuning(b"ntt_variant", 14)
         assert (outs[0] == outs[1]).all() and (outs[0] == outs[2]).all()
     # grouped inner product: group 0 = {v0, v1} (multi-vector: summed after the lift), group 1 = {v2 (shorter)}
     T = 9
@@ -296,15 +279,10 @@ def test_wide_kernels_equal_their_predecessors_and_the_oracle(name):
     kinds[4] = O.KIND_ONE
     vecs = [(dev.put(v[0]), kinds, 0), (dev.put(v[1]), None, 0), (dev.put(v[2]), None, 1)]
     res = {}
-    try:
-        for mv, pv in ((5, 1), (3, 0), (5, 0), (3, 1), (6, 1), (6, 0)):  # 6: one key vector in the 512-thread shape (mac_kernel_v4<13, ., 1>)
-            _set_tuning(b"mac_variant", mv)
-            _set_tuning(b"plain_variant", pv)
+    for mv, pv in ((5, 1), (3, 0), (5, 0), (3, 1), (6, 1), (6, 0)):  # 6: one key vector in the 512-thread shape (mac_kernel_v4<13, ., 1>)
+        with _lib.tuning(mac_variant=mv, plain_variant=pv):
             out, used = dev.msm([dev.put(encs)], vecs, 2, want_used=True)
             res[(mv, pv)] = (host(out), used)
-    finally:
-        _set_tuning(b"mac_variant", 5)
-        _set_tuning(b"plain_variant", 1)
     ref = res[(3, 0)]
     for k, r in res.items():
         assert r[1] == ref[1], k
@@ -323,7 +301,6 @@ def test_wide_kernels_equal_their_predecessors_and_the_oracle(name):
                                           ("toy60", 16, "wide"), ("toy60", 64, "chain"), ("toy60", 600, "wide"), ("toy60", 90, "many_inputs"),
                                           ("toy+int", 33, "wide"), ("toy49+int", 64, "chain")])
 def test_witness_map_matches_oracle(name, m, kind):
-    from ringsnark_amd import _lib
     dev = dev_for(name)
     prm = dev.prm
     ctx = H.oracle_ctx(prm)
@@ -362,7 +339,6 @@ def test_polynomial_coefficients_match_oracle(name, m, aux_only, zk, lds):
     benchmarks/bench_ntt_SEAL.cpp:46-53): evaluate in its three modes, the whole witness map and both provers against
     the oracle.  aux_only keeps the linear-form io vectors (no polynomial on the constant one or an input); otherwise
     the generic io path and the per-slot constant part of the mid vectors run.  lds = 6 forces the multi-pass columns."""
-    from ringsnark_amd import _lib
     dev = dev_for(name)
     prm = dev.prm
     ctx = H.oracle_ctx(prm)
@@ -381,8 +357,7 @@ def test_polynomial_coefficients_match_oracle(name, m, aux_only, zk, lds):
                 assert (got[:, limb, :] == O.r1cs_evaluate(prm.q[limb], ocs, which, limb, np.ascontiguousarray(part[:, limb, :]))).all(), (which, mode)
     ds = [ctx.random_ring(60 + k) for k in range(3)] if zk else [None] * 3
     dds = [dev.put(d) if d is not None else None for d in ds]
-    _set_tuning(b"witness_lds_logM", lds)
-    try:
+    with _lib.tuning(witness_lds_logM=lds):
         w = dev.witness_map(dcs, dasg, *dds)
         got = {k: host(v) if k != "Z" else v for k, v in w.items()}
         pk = dict(s_pows=ctx.random_enc(71, m + 1), delta_ts=ctx.random_enc(72, m + 1), delta_mid=ctx.random_enc(73, cs.n_aux),
@@ -393,8 +368,6 @@ def test_polynomial_coefficients_match_oracle(name, m, aux_only, zk, lds):
                   beta_rv_ts=ctx.random_enc(84), beta_rw_ts=ctx.random_enc(85), beta_ry_ts=ctx.random_enc(86))
         rp, rempty = dev.rinocchio_prove(dcs, {k: dev.put(v) for k, v in rk.items()}, dasg, *dds)
         rp = host(rp)
-    finally:
-        _set_tuning(b"witness_lds_logM", 13)
     for limb in range(prm.L):
         dl = [np.ascontiguousarray(d[limb]) if d is not None else None for d in ds]
         exp = O.witness_map(prm.q[limb], ocs, limb, np.ascontiguousarray(asg[:, limb, :]), *dl)
@@ -428,11 +401,8 @@ def test_polynomial_coefficients_on_slot_ranges_chunks_and_recipe_primes(name, m
     for limb in range(prm.L):
         for k in keys:
             assert (host(w[k])[:, limb, :] == exp[limb][k][:, s0:s0 + ns]).all(), (k, limb)
-    _set_tuning(b"witness_col_budget_mib", 1)  # chunks of at most 64 columns
-    try:
+    with _lib.tuning(witness_col_budget_mib=1):  # chunks of at most 64 columns
         w = dev.witness_map(dcs, dasg, *dds)
-    finally:
-        _set_tuning(b"witness_col_budget_mib", 16 * 1024)
     for limb in range(prm.L):
         for k in keys:
             assert (host(w[k])[:, limb, :] == exp[limb][k]).all(), (k, limb)
@@ -519,11 +489,6 @@ def test_rinocchio_prover_matches_oracle(name, m, zk):
         assert (g[k] == exp[k]).all(), k
 
 
-def _set_tuning(key, value):
-    from ringsnark_amd import _lib
-    _lib.check(_lib.load().rs_set_tuning(key, value))
-
-
 @pytest.mark.parametrize("name,m,kind,zk", [("toy", 70, "wide", False), ("toy", 300, "wide", True), ("toy", 1000, "chain", True),
                                              ("toy", 513, "many_inputs", False), ("toy60", 300, "wide", True), ("toy54", 513, "many_inputs", False)])
 def test_witness_map_multipass_matches_oracle(name, m, kind, zk):
@@ -536,12 +501,9 @@ def test_witness_map_multipass_matches_oracle(name, m, kind, zk):
           "many_inputs": lambda: R.wide_r1cs(m, prm.q, n_inputs=70)}[kind]()
     asg = H.make_assignment(ctx, cs)
     ds = [ctx.random_ring(60 + k) for k in range(3)] if zk else [None] * 3
-    _set_tuning(b"witness_lds_logM", 6)
-    try:
+    with _lib.tuning(witness_lds_logM=6):
         w = dev.witness_map(dev.r1cs(cs), dev.put(asg), *[dev.put(d) if d is not None else None for d in ds])
         got = {k: host(v) if k != "Z" else v for k, v in w.items()}
-    finally:
-        _set_tuning(b"witness_lds_logM", 13)
     ocs = H.oracle_cs(cs)
     for limb in range(prm.L):
         dl = [np.ascontiguousarray(d[limb]) if d is not None else None for d in ds]
@@ -561,12 +523,9 @@ def test_groth16_prover_multipass_matches_oracle():
     pk = dict(s_pows=ctx.random_enc(71, m + 1), delta_ts=ctx.random_enc(72, m + 1), delta_mid=ctx.random_enc(73, cs.n_aux),
               alpha=ctx.random_enc(74), beta=ctx.random_enc(75))
     exp, exp_empty = O.groth16_prove(ctx, H.oracle_cs(cs), pk, asg)
-    _set_tuning(b"witness_lds_logM", 7)
-    try:
+    with _lib.tuning(witness_lds_logM=7):
         got, empty = dev.groth16_prove(dev.r1cs(cs), {k: dev.put(v) for k, v in pk.items()}, dev.put(asg))
         g = host(got)
-    finally:
-        _set_tuning(b"witness_lds_logM", 13)
     assert empty == exp_empty and (g == exp).all()
 
 
@@ -650,7 +609,6 @@ def test_c4_shape_rinocchio_configuration():
     N_enc = 16384 with K = 8): transforms, the inner product (with its special terms) and a small
     Rinocchio proof, bit-exact against the oracle.  N_enc = 16384 takes the generic MAC kernel and
     the 136 KiB-tile transforms."""
-    from ringsnark_amd import _lib
     dev = dev_for("C4")
     prm = dev.prm
     ctx = H.oracle_ctx(prm)
@@ -787,8 +745,7 @@ def test_witness_map_slot_ranges_and_chunks_equal_the_whole(name, m, kind, zk):
         part = dev.witness_map_slots(dcs, asg, slot0, ns, *ds)
         for k in keys:
             assert (host(part[k]) == full[k][:, :, slot0:slot0 + ns]).all(), (k, slot0, ns)
-    _set_tuning(b"witness_col_budget_mib", 1)
-    try:
+    with _lib.tuning(witness_col_budget_mib=1):
         again = dev.witness_map(dcs, asg, *ds)
         for k in keys:
             assert (host(again[k]) == full[k]).all(), k
@@ -796,8 +753,6 @@ def test_witness_map_slot_ranges_and_chunks_equal_the_whole(name, m, kind, zk):
         sub = dev.witness_map(dcs, asg, *ds, want=("A_io", "A_mid", "B_io", "B_mid", "H"))
         for k in ("A_io", "A_mid", "B_io", "B_mid", "H"):
             assert (host(sub[k]) == full[k]).all(), k
-    finally:
-        _set_tuning(b"witness_col_budget_mib", 16 * 1024)
 
 
 @pytest.mark.parametrize("name,m,kind,zk", [("toy", 40, "wide", True), ("toy", 64, "chain", False), ("toy", 100, "many_inputs", True),
@@ -881,7 +836,6 @@ def test_witness_map_row_ranges_are_validated():
     """rs_witness_map_rows refuses ranges outside a vector and different ranges for the io and mid vectors of one matrix
     (one pass writes both)."""
     import ctypes as C
-    from ringsnark_amd import _lib
     from ringsnark_amd.device import _ptr
     dev = dev_for("toy")
     prm = dev.prm
@@ -966,8 +920,7 @@ def test_host_resident_key_equals_the_device_resident_one(name, tile):
     hk = {k: (on_host(v) if v.ndim == 5 else dev.put(v)) for k, v in pk.items()}
     dk = {k: dev.put(v) for k, v in pk.items()}
     dcs, dasg = dev.r1cs(cs), dev.put(asg)
-    _set_tuning(b"msm_host_tile", tile)
-    try:
+    with _lib.tuning(msm_host_tile=tile):
         got_h, empty_h = dev.groth16_prove(dcs, hk, dasg)
         rings = ctx.random_ring(32, m + 1)
         kinds = np.zeros(m + 1, dtype=np.uint8)
@@ -981,8 +934,6 @@ def test_host_resident_key_equals_the_device_resident_one(name, tile):
         # and is staged by two copies (round-3 advice: the single copy read past the end of the host buffer)
         w12 = on_host(pk["s_pows"][:12])
         ip_w12, _ = dev.msm([w12], [(dev.put(rings), kinds, 0)], 1, crs_len=m + 1, window=12)
-    finally:
-        _set_tuning(b"msm_host_tile", 1024)
     got_d, empty_d = dev.groth16_prove(dcs, dk, dasg)
     assert empty_h == empty_d and (host(got_h) == host(got_d)).all()
     if prm.N_enc <= 128:
@@ -1012,35 +963,25 @@ def test_multipass_tuned_sub_transform_kernel_equals_generic(m, zk):
     ds = [dev.put(ctx.random_ring(60 + k)) for k in range(3)] if zk else [None] * 3
     dcs = dev.r1cs(cs)
     keys = ("A_io", "B_io", "C_io", "A_mid", "B_mid", "C_mid", "H")
-    from tests.witness_knobs import SUB_CT_DEFAULT
     runs = {}
-    from ringsnark_amd import _lib
-    try:
-        for variant in (0, 1, 2, 3):  # generic, wave-private tuned (sub_ntt_ct_kernel), wide (sub_ntt_wide_kernel), wide16
+    for variant in (0, 1, 2, 3):  # generic, wave-private tuned (sub_ntt_ct_kernel), wide (sub_ntt_wide_kernel), wide16
+        with contextlib.ExitStack() as knob:
             try:
-                _set_tuning(b"witness_sub_ct", variant)
+                knob.enter_context(_lib.tuning(witness_sub_ct=variant))
             except _lib.RsError as e:  # 1 and 3 are superseded A/B variants: experiments build only
                 assert variant in (1, 3) and e.code == _lib.RS_ERR_UNSUPPORTED
                 continue
             runs[variant] = {k: host(v) for k, v in dev.witness_map(dcs, asg, *ds).items() if k in keys}
-    finally:
-        _set_tuning(b"witness_sub_ct", SUB_CT_DEFAULT)
     assert 0 in runs and 2 in runs
     for variant in runs:
         for k in keys:
             assert (runs[variant][k] == runs[0][k]).all(), (variant, k)
     # the product-tree kernels of the 2^13 tiles: level loop not unrolled (0), wave-private radix-8 (1), wide (2)
-    from tests.witness_knobs import TREE_CT_DEFAULT
-    try:
-        for variant, tile in ((0, 13), (1, 13), (2, 13), (2, 14)):  # the wide kernel on 2^13 and on 2^14 tiles
-            _set_tuning(b"witness_tree_ct", variant)
-            _set_tuning(b"witness_tree_log", tile)
+    for variant, tile in ((0, 13), (1, 13), (2, 13), (2, 14)):  # the wide kernel on 2^13 and on 2^14 tiles
+        with _lib.tuning(witness_tree_ct=variant, witness_tree_log=tile):
             got = {k: host(v) for k, v in dev.witness_map(dcs, asg, *ds).items() if k in keys}
             for k in keys:
                 assert (got[k] == runs[0][k]).all(), ("tree", variant, tile, k)
-    finally:
-        _set_tuning(b"witness_tree_ct", TREE_CT_DEFAULT)
-        _set_tuning(b"witness_tree_log", 14)
 
 
 @pytest.mark.parametrize("m,zk", [(20000, True), (40000, False), (65536, True)])
@@ -1057,10 +998,7 @@ def test_two_dimensional_block_convolutions_equal_the_other_paths(m, zk):
     keys = ("A_io", "B_io", "C_io", "A_mid", "B_mid", "C_mid", "H")
     runs = {}
     for label, force, bc2, inc in (("full-length", 0, 1, 1), ("two-dimensional", 14, 1, 0), ("pairwise", 14, 0, 0), ("incomplete", 14, 1, 1)):
-        _set_tuning(b"witness_force_bc", force)
-        _set_tuning(b"witness_bc2", bc2)
-        _set_tuning(b"witness_inc", inc)  # 1 (the default since round 6): such primes run incomplete transforms, not block convolutions
-        try:
+        with _lib.tuning(witness_force_bc=force, witness_bc2=bc2, witness_inc=inc):  # inc = 1: incomplete transforms, not block convolutions
             dev = Device(prm)  # fresh context: plans are cached per context
             asg = dev.ring_empty(m + 2)
             dev.fill_uniform(asg[:2], 0, 9)
@@ -1074,10 +1012,6 @@ def test_two_dimensional_block_convolutions_equal_the_other_paths(m, zk):
             assert ("bc_mac_kernel" in names) == (label == "pairwise"), (label, names)
             assert any(n.startswith("sub_ntt_w") and not n.endswith(", 0>") for n in names) == (label == "incomplete"), (label, names)
             del dev, asg
-        finally:
-            _set_tuning(b"witness_force_bc", 0)
-            _set_tuning(b"witness_bc2", 1)
-            _set_tuning(b"witness_inc", 1)
     for label in ("two-dimensional", "pairwise", "incomplete"):
         for k in keys:
             assert (runs[label][k] == runs["full-length"][k]).all(), (label, k)
@@ -1106,7 +1040,6 @@ def test_multipass_production_tile_matches_oracle_on_a_few_slots():
 def test_poly_multiply_add_divide_match_oracle(name):
     """Row a11 (util/polynomials.tcc:62-81): per-slot polynomial product / sum / quotient with ring-element
     coefficients, non-monic per-slot divisors included, against the oracle's schoolbook restatement."""
-    from ringsnark_amd import _lib
     dev = dev_for(name)
     prm = dev.prm
     ctx = H.oracle_ctx(prm)
@@ -1163,8 +1096,7 @@ def test_witness_map_block_convolution_path_matches_oracle(name, bc, m, kind, zk
     if bc == 0:
         need = (m - 1).bit_length() + 1
         assert min(P.two_adicity(q) for q in prm.q) < need, "preset happens to have enough 2-adicity; pick a larger m"
-    _set_tuning(b"witness_force_bc", bc)
-    try:
+    with _lib.tuning(witness_force_bc=bc):
         dev = Device(prm)  # fresh context: plans are cached per context
         ctx = H.oracle_ctx(prm)
         cs = {"wide": lambda: R.wide_r1cs(m, prm.q), "chain": lambda: R.chain_r1cs(m, prm.q),
@@ -1173,8 +1105,6 @@ def test_witness_map_block_convolution_path_matches_oracle(name, bc, m, kind, zk
         ds = [ctx.random_ring(60 + k) for k in range(3)] if zk else [None] * 3
         w = dev.witness_map(dev.r1cs(cs), dev.put(asg), *[dev.put(d) if d is not None else None for d in ds])
         got = {k: host(v) if k != "Z" else v for k, v in w.items()}
-    finally:
-        _set_tuning(b"witness_force_bc", 0)
     ocs = H.oracle_cs(cs)
     for limb in range(prm.L):
         dl = [np.ascontiguousarray(d[limb]) if d is not None else None for d in ds]

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from ringsnark_amd import _lib
 from ringsnark_amd import params as P
 from ringsnark_amd import r1cs as R
 from tests import helpers as H
@@ -22,28 +23,6 @@ from tests import proof_check
 pytestmark = pytest.mark.gpu
 
 KEYS = ("A_io", "B_io", "C_io", "A_mid", "B_mid", "C_mid", "H")
-
-
-def _set_tuning(key, value):
-    from ringsnark_amd import _lib
-    _lib.check(_lib.load().rs_set_tuning(key, value))
-
-
-class _knobs:
-    """Set tuning knobs, restore the library defaults on exit (plans read them when they are built: use a fresh Device inside)."""
-    DEFAULTS = {b"witness_lds_logM": 13, b"witness_force_bc": 0, b"witness_inc": 1, b"witness_bc2": 1, b"force_int_arith": 0,
-                b"witness_sub_log": 12, b"witness_sub_ct": 2}
-
-    def __init__(self, **kv):
-        self.kv = {k.encode(): v for k, v in kv.items()}
-
-    def __enter__(self):
-        for k, v in self.kv.items():
-            _set_tuning(k, v)
-
-    def __exit__(self, *exc):
-        for k in self.kv:
-            _set_tuning(k, self.DEFAULTS[k])
 
 
 def _host(t):
@@ -67,7 +46,7 @@ def test_incomplete_transforms_match_oracle(name, lds, force, m, kind, zk):
     from ringsnark_amd.device import Device
     prm = P.preset(name)
     int_arith = kind == "int"
-    with _knobs(witness_lds_logM=lds, witness_force_bc=force, force_int_arith=int(int_arith)):
+    with _lib.tuning(witness_lds_logM=lds, witness_force_bc=force, force_int_arith=int(int_arith)):
         dev = Device(prm)
         ctx = H.oracle_ctx(prm)
         cs = {"wide": lambda: R.wide_r1cs(m, prm.q), "int": lambda: R.wide_r1cs(m, prm.q), "chain": lambda: R.chain_r1cs(m, prm.q),
@@ -95,7 +74,7 @@ def test_rinocchio_and_groth16_provers_on_incomplete_transforms_match_oracle():
     from ringsnark_amd.device import Device
     prm = P.preset("toyR")
     m = 150  # 2M = 2^9 on 2-adicity 7
-    with _knobs(witness_lds_logM=6):
+    with _lib.tuning(witness_lds_logM=6):
         dev, ctx = Device(prm), H.oracle_ctx(prm)
         cs = R.wide_r1cs(m, prm.q)
         asg = H.make_assignment(ctx, cs)
@@ -125,7 +104,7 @@ def _run_large(prm, m, zk, want=KEYS, **knobs):
     from ringsnark_amd.device import Device
     octx = H.oracle_ctx(prm)
     cs = R.chain_r1cs(m, prm.q)
-    with _knobs(**knobs):
+    with _lib.tuning(**knobs):
         dev = Device(prm)  # fresh context: plans are cached per context and read the knobs when they are built
         asg = dev.ring_empty(m + 2)
         dev.fill_uniform(asg[:2], 0, 9)

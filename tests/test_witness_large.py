@@ -12,6 +12,7 @@ and H Z = A B - C (+ the ZK patch), plus bit-equality of the two paths with each
 import numpy as np
 import pytest
 
+from ringsnark_amd import _lib
 from ringsnark_amd import params as P
 from ringsnark_amd import r1cs as R
 from tests import helpers as H
@@ -19,13 +20,7 @@ from tests import proof_check
 
 pytestmark = pytest.mark.gpu
 
-SUB_LOG_DEFAULT = 12  # the library default of the knob witness_sub_log
 KEYS = ("A_io", "B_io", "C_io", "A_mid", "B_mid", "C_mid", "H")
-
-
-def _set_tuning(key, value):
-    from ringsnark_amd import _lib
-    _lib.check(_lib.load().rs_set_tuning(key, value))
 
 
 def _run(prm, m, zk, force, int_arith=False, want=KEYS, inc=None):
@@ -37,16 +32,9 @@ def _run(prm, m, zk, force, int_arith=False, want=KEYS, inc=None):
     from ringsnark_amd.device import Device
     octx = H.oracle_ctx(prm)
     cs = R.chain_r1cs(m, prm.q)
-    _set_tuning(b"witness_force_bc", force)
-    _set_tuning(b"witness_inc", (0 if force else 1) if inc is None else inc)
-    if int_arith:
-        _set_tuning(b"force_int_arith", 1)
-    try:
-        dev = Device(prm)
-    finally:
-        if int_arith:
-            _set_tuning(b"force_int_arith", 0)
-    try:
+    with _lib.tuning(witness_force_bc=force, witness_inc=(0 if force else 1) if inc is None else inc):
+        with _lib.tuning(**(dict(force_int_arith=1) if int_arith else {})):
+            dev = Device(prm)
         asg = dev.ring_empty(m + 2)
         dev.fill_uniform(asg[:2], 0, 9)
         dev.chain_assignment(asg, m)
@@ -56,9 +44,6 @@ def _run(prm, m, zk, force, int_arith=False, want=KEYS, inc=None):
         torch.cuda.synchronize()
         names = {k["name"] for k in dev.profile_read()}
         dev.set_profiling(False)
-    finally:
-        _set_tuning(b"witness_force_bc", 0)
-        _set_tuning(b"witness_inc", 1)
     return dev, cs, asg, ds, w, names
 
 
@@ -116,11 +101,8 @@ def test_wide_cross_passes_equal_the_radix_16_ones(m):
     prm = P.preset("toy44")
     runs = {}
     for maxr in (4, 6):
-        _set_tuning(b"witness_cross_maxr", maxr)
-        try:
+        with _lib.tuning(witness_cross_maxr=maxr):
             dev, cs, asg, ds, w, names = _run(prm, m, True, 0)
-        finally:
-            _set_tuning(b"witness_cross_maxr", 6)
         wide = [n for n in names if n.startswith("cross_kernel<") and n.split(",")[1].strip() in ("5", "6")]
         assert bool(wide) == (maxr == 6), names
         runs[maxr] = {k: to_host(w[k]) for k in KEYS}
@@ -139,13 +121,8 @@ def test_sub_transform_blocks_of_2_12_equal_2_13(m, cross):
     prm = P.preset("toy44")
     runs = {}
     for logb in (13, 12):
-        _set_tuning(b"witness_sub_log", logb)
-        _set_tuning(b"witness_sub12_cross", cross)
-        try:
+        with _lib.tuning(witness_sub_log=logb, witness_sub12_cross=cross):
             dev, cs, asg, ds, w, names = _run(prm, m, True, 0)
-        finally:
-            _set_tuning(b"witness_sub_log", SUB_LOG_DEFAULT)
-            _set_tuning(b"witness_sub12_cross", 4)
         assert any(n.startswith("sub_ntt_w12_kernel") for n in names) == (logb == 12), names
         if logb == 12:
             assert any(n.startswith("sub_ntt_wide_kernel") for n in names) == (cross == 4 and m > 32768), names
@@ -167,11 +144,8 @@ def test_h_on_a_coset_equals_the_long_division_form(m, zk, int_arith):
     prm = P.preset("toy44")
     runs = {}
     for coset in (0, 1):
-        _set_tuning(b"witness_h_coset", coset)
-        try:
+        with _lib.tuning(witness_h_coset=coset):
             dev, cs, asg, ds, w, names = _run(prm, m, zk, 0, int_arith=int_arith)
-        finally:
-            _set_tuning(b"witness_h_coset", 1)
         assert any("<4" in n and n.startswith("sub_ntt") for n in names) == (coset == 1), names
         if coset:
             err, info = proof_check.check_all_columns(prm, cs, asg, {k: w[k] for k in KEYS}, tuple(ds), seed=m % 1000, Z=w["Z"])
@@ -220,8 +194,7 @@ def test_unsatisfied_assignment_long_division_and_coset_forms():
     m = 20000
     runs = {}
     for tag, coset, want in (("long", 0, KEYS), ("coset", 1, KEYS), ("no_c", 1, ("A_mid", "B_mid", "H"))):
-        _set_tuning(b"witness_h_coset", coset)
-        try:
+        with _lib.tuning(witness_h_coset=coset):
             dev = Device(prm)
             cs = R.chain_r1cs(m, prm.q)
             asg = dev.ring_empty(m + 2)
@@ -230,8 +203,6 @@ def test_unsatisfied_assignment_long_division_and_coset_forms():
             asg[777, 0, 3] += 1  # one wire of one column no longer satisfies its constraints
             w = dev.witness_map(dev.r1cs(cs), asg, want=want)
             runs[tag] = {k: to_host(w[k]) for k in want}
-        finally:
-            _set_tuning(b"witness_h_coset", 1)
         del dev, asg, w
     for k in ("A_mid", "B_mid"):
         assert (runs["long"][k] == runs["coset"][k]).all() and (runs["long"][k] == runs["no_c"][k]).all()
@@ -253,15 +224,11 @@ def test_product_tree_tiles_in_one_launch_per_chunk(force):
     prm = P.preset("toy44")
     m = 100000
     runs = {}
-    for tag, ws, once in (("default", 6144, 1), ("sub-chunks, one tree launch", 64, 1), ("sub-chunks, tree per sub-chunk", 64, 0)):
-        _set_tuning(b"witness_big_ws_mib", ws)
-        _set_tuning(b"witness_tree_once", once)
-        try:
+    for tag, knobs in (("default", {}), ("sub-chunks, one tree launch", dict(witness_big_ws_mib=64)),
+                       ("sub-chunks, tree per sub-chunk", dict(witness_big_ws_mib=64, witness_tree_once=0))):
+        with _lib.tuning(**knobs):
             dev, cs, asg, ds, w, names = _run(prm, m, True, force)
-        finally:
-            _set_tuning(b"witness_big_ws_mib", 6144)
-            _set_tuning(b"witness_tree_once", 1)
-        if ws == 64 and once:
+        if tag == "sub-chunks, one tree launch":
             err, info = proof_check.check_all_columns(prm, cs, asg, {k: w[k] for k in KEYS}, tuple(ds), seed=4, Z=w["Z"])
             assert err is None and info["columns"] == prm.L * prm.N, err
         runs[tag] = {k: to_host(w[k]) for k in KEYS}
@@ -303,11 +270,8 @@ def test_the_turn_of_h_as_one_pass(m, zk, int_arith):
     prm = P.preset("toy44")
     runs = {}
     for turn in (0, 1):
-        _set_tuning(b"witness_h_turn", turn)
-        try:
+        with _lib.tuning(witness_h_turn=turn):
             dev, cs, asg, ds, w, names = _run(prm, m, zk, 0, int_arith=int_arith, want=("A_mid", "B_mid", "H"))
-        finally:
-            _set_tuning(b"witness_h_turn", 1)
         assert any(n.startswith("cross_turn_kernel") for n in names) == (turn == 1), names
         if turn:
             err, info = proof_check.check_all_columns(prm, cs, asg, {k: w[k] for k in ("A_mid", "B_mid", "H")}, tuple(ds), seed=m % 991, Z=w["Z"])
@@ -329,11 +293,8 @@ def test_the_turn_between_tree_levels_as_one_pass(m, zk, int_arith):
     prm = P.preset("toy44")
     runs = {}
     for turn in (0, 1):
-        _set_tuning(b"witness_level_turn", turn)
-        try:
+        with _lib.tuning(witness_level_turn=turn):
             dev, cs, asg, ds, w, names = _run(prm, m, zk, 0, int_arith=int_arith, want=("A_mid", "B_mid", "C_mid", "H"))
-        finally:
-            _set_tuning(b"witness_level_turn", 1)
         assert any(n.startswith("cross_level_turn_kernel") for n in names) == (turn == 1), names
         if turn:
             err, info = proof_check.check_all_columns(prm, cs, asg, {k: w[k] for k in ("A_mid", "B_mid", "C_mid", "H")}, tuple(ds),
@@ -359,15 +320,8 @@ def test_level_15_forward_stages_inside_the_tile_kernel(m, zk, sub_log, ws):
     runs = {}
     want = ("A_mid", "B_mid", "C_mid", "H")
     for fwd in (0, 1):
-        _set_tuning(b"witness_tree_fwd", fwd)
-        _set_tuning(b"witness_sub_log", sub_log)
-        _set_tuning(b"witness_big_ws_mib", ws)
-        try:
+        with _lib.tuning(witness_tree_fwd=fwd, witness_sub_log=sub_log, witness_big_ws_mib=ws):
             dev, cs, asg, ds, w, names = _run(prm, m, zk, 0, want=want)
-        finally:
-            _set_tuning(b"witness_tree_fwd", 0)
-            _set_tuning(b"witness_sub_log", SUB_LOG_DEFAULT)
-            _set_tuning(b"witness_big_ws_mib", 6144)
         rf = 3 if sub_log == 12 else 2
         assert (("tree_wide_kernel<14, %d>" % rf) in names) == (fwd == 1), names
         if fwd:
@@ -390,13 +344,8 @@ def test_the_turns_on_the_two_dimensional_block_convolutions(m, zk):
     want = ("A_mid", "B_mid", "C_mid", "H")
     runs = {}
     for turn in (0, 1):
-        _set_tuning(b"witness_h_turn", turn)
-        _set_tuning(b"witness_level_turn", turn)
-        try:
+        with _lib.tuning(witness_h_turn=turn, witness_level_turn=turn):
             dev, cs, asg, ds, w, names = _run(prm, m, zk, 14, want=want)
-        finally:
-            _set_tuning(b"witness_h_turn", 1)
-            _set_tuning(b"witness_level_turn", 1)
         logM = (m - 1).bit_length()
         assert ("bc2_h_turn_kernel" in names) == (turn == 1 and logM <= 16), names
         assert ("bc2_level_turn_kernel" in names) == (turn == 1 and logM >= 16), names

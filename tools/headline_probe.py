@@ -16,9 +16,7 @@ prm = P.preset(sys.argv[4] if len(sys.argv) > 4 else "C3")
 dev = Device(prm)
 import os  # noqa: E402
 from ringsnark_amd import _lib  # noqa: E402
-for kv in os.environ.get("RS_TUNING", "").split(","):  # e.g. RS_TUNING=witness_sub_ct=2,ntt_variant=12
-    if "=" in kv:
-        _lib.check(_lib.load().rs_set_tuning(kv.split("=")[0].encode(), int(kv.split("=")[1])))
+_lib.tuning_from_env()  # e.g. RS_TUNING=witness_sub_ct=2,ntt_variant=12
 m, W = 1 << logm, 1 << logw
 t0 = time.time()
 cs = R.chain_r1cs(m, prm.q)

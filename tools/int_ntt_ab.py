@@ -3,12 +3,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ringsnark_amd import _lib, params as P
 from ringsnark_amd.device import Device
-prm = P.preset("micro60"); dev = Device(prm); lib = _lib.load()
+prm = P.preset("micro60"); dev = Device(prm)
 batch = (1 << 30) // (prm.N_enc * 8)
 src = torch.empty((batch, prm.N_enc), dtype=torch.int64, device=dev.device).random_(0, int(prm.Q[0]))
 ref = None
 for v in (0, 1, 0, 1):
-    _lib.check(lib.rs_set_tuning(b"int_ntt_variant", v))
+    _lib.set_tuning("int_ntt_variant", v)
     d = src.clone(); dev.ntt(d, _lib.RS_MOD_COEFF, 0); f = d.clone(); dev.ntt(d, _lib.RS_MOD_COEFF, 0, inverse=True)
     rt = bool((d == src).all()); ref = f if ref is None else ref
     res = []

@@ -1,4 +1,4 @@
-"""A/B of one rs_set_tuning knob on one GPU: the headline ringGroth16 proof (C3, 2^16 constraints, window 2^13) and the
+"""A/B of one tuning knob on one GPU: the headline ringGroth16 proof (C3, 2^16 constraints, window 2^13) and the
 configs[3]-shape Rinocchio proof (C4, 2^12 constraints, window 2^9), per-kernel times of the inner products.
 usage: tools/knob_ab.py <knob> <value,value,...> [groth16|rinocchio|both]      KNOB_AB_KERNELS=prefix,prefix: the kernels listed"""
 import os
@@ -11,17 +11,15 @@ import torch
 from ringsnark_amd import _lib, params as P, r1cs as R
 from ringsnark_amd.device import Device
 
-knob, values = sys.argv[1].encode(), [int(v) for v in sys.argv[2].split(",")]
+knob, values = sys.argv[1], [int(v) for v in sys.argv[2].split(",")]
 which = sys.argv[3] if len(sys.argv) > 3 else "both"
 PREFIXES = tuple(os.environ.get("KNOB_AB_KERNELS", "mac_,plain_").split(","))
-lib = _lib.load()
-for kv in filter(None, os.environ.get("KNOB_AB_SET", "").split(",")):  # other knobs held fixed: KNOB_AB_SET=key=value,key=value
-    _lib.check(lib.rs_set_tuning(kv.split("=")[0].encode(), int(kv.split("=")[1])))
+_lib.tuning_from_env("KNOB_AB_SET")  # other knobs held fixed: KNOB_AB_SET=key=value,key=value
 
 
 def run(tag, dev, prove, m):
     for v in values:
-        _lib.check(lib.rs_set_tuning(knob, v))
+        _lib.set_tuning(knob, v)
         for _ in range(2):
             prove()
         torch.cuda.synchronize()
@@ -34,7 +32,7 @@ def run(tag, dev, prove, m):
         dt = (time.time() - t0) / 3
         ks = dev.profile_read()
         dev.set_profiling(False)
-        print("%s %s=%d: %.1f ms/proof (%.0f constraints/s)  " % (tag, knob.decode(), v, dt * 1e3, m / dt) +
+        print("%s %s=%d: %.1f ms/proof (%.0f constraints/s)  " % (tag, knob, v, dt * 1e3, m / dt) +
               "  ".join("%s %.1f" % (k["name"][:28], k["total_ms"] / 3) for k in ks if k["name"].startswith(PREFIXES)), flush=True)
 
 

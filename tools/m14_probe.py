@@ -5,9 +5,8 @@ sys.path.insert(0, ".")
 import torch
 from ringsnark_amd import params as P, r1cs as R, _lib
 from ringsnark_amd.device import Device
-lib=_lib.load()
 for inc in (1, 0):
-    _lib.check(lib.rs_set_tuning(b"witness_inc", inc))
+    _lib.set_tuning("witness_inc", inc)
     prm = P.preset("C3"); dev = Device(prm)
     for m in (12000, 16384):
         cs = R.chain_r1cs(m, prm.q); dcs = dev.r1cs(cs)

@@ -17,7 +17,6 @@ W = (1 << int(sys.argv[3])) if len(sys.argv) > 3 else 512
 units = [int(u) for u in sys.argv[4].split(",")] if len(sys.argv) > 4 else [768]
 dev = Device(prm)
 m = 1 << logm
-lib = _lib.load()
 nk = (lambda T: min(T, W) if W else T)
 cs = R.chain_r1cs(m, prm.q)
 dcs = dev.r1cs(cs)
@@ -27,12 +26,10 @@ dev.chain_assignment(asg, m)
 pk = dict(s_pows=dev.fill_uniform(dev.enc_empty(nk(m + 1)), 1, 3), alpha_s_pows=dev.fill_uniform(dev.enc_empty(nk(m + 1)), 1, 4),
           beta_prods=dev.fill_uniform(dev.enc_empty(nk(m)), 1, 5), beta_rv_ts=dev.fill_uniform(dev.enc_empty(), 1, 6),
           beta_rw_ts=dev.fill_uniform(dev.enc_empty(), 1, 7), beta_ry_ts=dev.fill_uniform(dev.enc_empty(), 1, 8))
-for kv in os.environ.get("RS_TUNING", "").split(","):  # e.g. RS_TUNING=mac_share_keys=0
-    if "=" in kv:
-        _lib.check(lib.rs_set_tuning(kv.split("=")[0].encode(), int(kv.split("=")[1])))
+_lib.tuning_from_env()  # e.g. RS_TUNING=mac_share_keys=0
 dev.set_profiling(True)
 for u in units:
-    _lib.check(lib.rs_set_tuning(b"mac_chunk_units", u))
+    _lib.set_tuning("mac_chunk_units", u)
     for it in range(2):
         dev.rinocchio_prove(dcs, pk, asg, window=W)
     torch.cuda.synchronize()

@@ -3,15 +3,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ringsnark_amd import params as P, _lib
 from ringsnark_amd.device import Device
-prm = P.preset("C3"); dev = Device(prm); lib = _lib.load()
+prm = P.preset("C3"); dev = Device(prm)
 T = 4096
 crs = dev.enc_empty(T); dev.fill_uniform(crs, 1, 3)
 v = dev.ring_empty(T); dev.fill_uniform(v, 0, 10)
 dev.set_profiling(True)
 for variant in (1, 2, 3):
-    _lib.check(lib.rs_set_tuning(b"mac_variant", variant))
+    _lib.set_tuning("mac_variant", variant)
     for ab in ((0,) if variant == 1 else (0, 1, 2, 6)):
-        _lib.check(lib.rs_set_tuning(b"mac_ablate", ab))
+        _lib.set_tuning("mac_ablate", ab)
         for _ in range(2):
             import ctypes
             dev.lib.rs_groth16_prove  # noqa

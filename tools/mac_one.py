@@ -13,9 +13,7 @@ logw = int(sys.argv[2]) if len(sys.argv) > 2 else 12
 groups = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 prm = P.preset("C3")
 dev = Device(prm)
-for kv in os.environ.get("RS_TUNING", "").split(","):
-    if "=" in kv:
-        _lib.check(_lib.load().rs_set_tuning(kv.split("=")[0].encode(), int(kv.split("=")[1])))
+_lib.tuning_from_env()
 W = 1 << logw
 key = dev.fill_uniform(dev.enc_empty(W), 1, 13)
 vecs = [dev.fill_uniform(dev.ring_empty(terms), 0, 7 + g) for g in range(groups)]

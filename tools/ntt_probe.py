@@ -1,4 +1,4 @@
-"""Standalone NTT kernel shapes on one GPU (rs_set_tuning "ntt_variant"): one tool for what used to be four scripts.
+"""Standalone NTT kernel shapes on one GPU (tuning knob "ntt_variant"): one tool for what used to be four scripts.
 
   ntt_probe.py variants [preset] [v,v,...]   every variant: forward equals variant 0, round trip, forward / inverse GB/s
   ntt_probe.py one <variant> [inv] [preset]  three launches of one variant (the command to put under rocprofv3)
@@ -29,15 +29,14 @@ def timeit(fn, reps=10, warm=3):
 
 
 mode = sys.argv[1] if len(sys.argv) > 1 else "variants"
-lib = _lib.load()
-tune = lambda k, v: _lib.check(lib.rs_set_tuning(k, v))
+tune = _lib.set_tuning
 ints = lambda s: [int(x) for x in s.split(",")]
 B = 8192
 if mode == "one":
     v, inv = int(sys.argv[2]), len(sys.argv) > 3 and sys.argv[3] == "inv"
     prm = P.preset(sys.argv[4] if len(sys.argv) > 4 else "C3")
     dev = Device(prm)
-    tune(b"ntt_variant", v)
+    tune("ntt_variant", v)
     d = torch.empty((B, prm.N_enc), dtype=torch.int64, device=dev.device).random_(0, prm.Q[0])
     for _ in range(3):
         dev.ntt(d, _lib.RS_MOD_COEFF, 0, inverse=inv)
@@ -50,7 +49,7 @@ elif mode == "variants":
     gb = B * prm.N_enc * 16 / 1e9
     for v in (ints(sys.argv[3]) if len(sys.argv) > 3 else range(15)):
         try:
-            tune(b"ntt_variant", v)
+            tune("ntt_variant", v)
         except _lib.RsError as e:
             print("variant %d: %s" % (v, e))
             continue
@@ -70,19 +69,18 @@ elif mode in ("repeat", "stagger"):
     dev = Device(prm)
     d = torch.empty((B, prm.N_enc), dtype=torch.int64, device=dev.device).random_(0, prm.Q[0])
     for v in (ints(sys.argv[2]) if len(sys.argv) > 2 else (8, 9, 13)):
-        tune(b"ntt_variant", v)
+        tune("ntt_variant", v)
         if mode == "repeat":
             res = []
             for rep in (1, 5, 9):
-                tune(b"ntt_repeat", rep)
+                tune("ntt_repeat", rep)
                 res.append(timeit(lambda: dev.ntt(d, _lib.RS_MOD_COEFF, 0)))
             print("variant %d: 1x %.3f ms (%.0f GB/s), 5x %.3f, 9x %.3f -> %.1f ns per extra in-LDS transform" % (
                 v, res[0], B * 8192 * 16 / 1e6 / res[0], res[1], res[2], (res[2] - res[0]) / 8 / B * 1e6), flush=True)
         else:
             for stag in (0, 1, 2, 4, 8, 16):
-                tune(b"ntt_repeat", 1 + (stag << 8))
+                tune("ntt_repeat", 1 + (stag << 8))
                 ms = timeit(lambda: dev.ntt(d, _lib.RS_MOD_COEFF, 0))
                 print("variant %d stagger %d: %.3f ms  %.0f GB/s" % (v, stag, ms, B * 8192 * 16 / 1e6 / ms), flush=True)
-    tune(b"ntt_repeat", 1)
 else:
     sys.exit(__doc__)

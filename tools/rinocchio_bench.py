@@ -6,7 +6,7 @@ import torch
 from ringsnark_amd import params as P, r1cs as R, _lib
 from ringsnark_amd.device import Device
 logm = int(sys.argv[1]) if len(sys.argv) > 1 else 12
-prm = P.preset(sys.argv[2] if len(sys.argv) > 2 else "C3"); dev = Device(prm); m = 1 << logm; lib = _lib.load()
+prm = P.preset(sys.argv[2] if len(sys.argv) > 2 else "C3"); dev = Device(prm); m = 1 << logm
 W = (1 << int(sys.argv[3])) if len(sys.argv) > 3 else 0
 nk = (lambda T: min(T, W) if W else T)
 cs = R.chain_r1cs(m, prm.q); dcs = dev.r1cs(cs)
@@ -16,7 +16,7 @@ pk = dict(s_pows=dev.fill_uniform(dev.enc_empty(nk(m + 1)), 1, 3), alpha_s_pows=
           beta_rw_ts=dev.fill_uniform(dev.enc_empty(), 1, 7), beta_ry_ts=dev.fill_uniform(dev.enc_empty(), 1, 8))
 dev.set_profiling(True)
 for variant in (2, 3, 5):
-    _lib.check(lib.rs_set_tuning(b"mac_variant", variant))
+    _lib.set_tuning("mac_variant", variant)
     for it in range(3):
         torch.cuda.synchronize(); t0 = time.time()
         dev.rinocchio_prove(dcs, pk, asg, window=W); torch.cuda.synchronize()

@@ -9,7 +9,7 @@ prm = P.preset("C3"); prm = P.RingParams(prm.N, prm.q[:L_local], prm.N_enc, prm.
 dev = Device(prm); m = 1 << logm
 if len(sys.argv) > 4:
     from ringsnark_amd import _lib
-    _lib.check(_lib.load().rs_set_tuning(b"witness_lds_logM", int(sys.argv[4])))
+    _lib.set_tuning("witness_lds_logM", int(sys.argv[4]))
 cs = R.chain_r1cs(m, prm.q); dcs = dev.r1cs(cs)
 asg = dev.ring_empty(m + 2); dev.fill_uniform(asg[:2], 0, 7); dev.chain_assignment(asg, m)
 mt = m // tshare
