@@ -126,7 +126,7 @@ struct ProfRec {
   double bytes, fp64;
 };
 
-struct WitnessPlan;  // witness.hip
+struct WitnessPlan;  // witness_plan.hpp
 struct R1cs;         // r1cs in CSR on device
 
 }  // namespace rs
@@ -184,7 +184,7 @@ struct rs_ctx {
   int noise_tb = 0;
   void *d_crt_limbs = nullptr;
   std::mutex mu;
-  std::map<std::pair<size_t, uint64_t>, rs::WitnessPlan *> plans;  // keyed by (m, plan_knob_sig()), witness.hip get_plan
+  std::map<std::pair<size_t, uint64_t>, rs::WitnessPlan *> plans;  // keyed by (m, plan_knob_sig()), witness_plan.hip get_plan
   // workspace cache (grown on demand, per context; calls that need workspace serialise on mu)
   rs::DeviceBuf ws[16];
   hipStream_t cur_stream = nullptr;  // stream of the call that holds mu (rs::WsScope)

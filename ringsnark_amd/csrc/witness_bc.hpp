@@ -1,7 +1,8 @@
-// witness_bc.hpp -- block convolutions (pairwise and two-dimensional) for ring primes without a 2M-th root of unity: device kernels (witness.hip)
+// witness_bc.hpp -- block convolutions (pairwise and two-dimensional) for ring primes without a 2M-th root of unity: device kernels (witness_lds.hip)
 #pragma once
 #include "witness_cols.hpp"
 #include "witness_multipass.hpp"
+#include "witness_tree_wide.hpp"  // reg_fwd_stages_zu
 
 namespace rs {
 

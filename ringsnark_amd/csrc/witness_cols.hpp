@@ -1,4 +1,4 @@
-// witness_cols.hpp -- column plans, the column <-> boundary layout map and the transposes of the witness map (witness.hip)
+// witness_cols.hpp -- column plans, the column <-> boundary layout map and the transposes of the witness map (every witness*.hip unit)
 #pragma once
 #include "ntt_core.hpp"
 #include "ntt_wide.hpp"

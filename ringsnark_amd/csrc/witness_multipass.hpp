@@ -1,7 +1,10 @@
-// witness_multipass.hpp -- multi-pass column transforms: cross passes over global memory and rooted LDS sub-transforms (witness.hip)
+// witness_multipass.hpp -- multi-pass column transforms: cross passes over global memory and rooted LDS sub-transforms (witness_big.hip; sub_ntt_kernel: witness_lds.hip)
 #pragma once
 #include "witness_cols.hpp"
 #include "witness_inc.hpp"
+#ifdef RS_EXPERIMENTS
+#include "witness_tiles.hpp"  // TreeMulFactory (sub_ntt_ct_kernel)
+#endif
 
 namespace rs {
 
@@ -339,7 +342,7 @@ __global__ void __launch_bounds__(256) cross_kernel(CrossArgs a, CPS plans) {
 }
 
 // ---- the turn of H (round 5): the LAST inverse cross pass of P = A B and the FIRST forward cross pass of T = rev(P) mod
-// x^(m-1), as ONE pass over memory.  big_h (witness.hip) runs "inverse cross stages of the product, in place" and then
+// x^(m-1), as ONE pass over memory.  big_h (witness_big.hip) runs "inverse cross stages of the product, in place" and then
 // "forward cross stages of the reversed, truncated product, from W2 into W1": two HBM-bound passes, 7 n words of traffic per
 // column (n = 2M), of which the second re-reads what the first has just written.  Both passes hold a RESIDUE CLASS mod
 // B = n / 2^R in a thread -- the inverse one positions rho + e B, the forward one positions j + e' B -- and

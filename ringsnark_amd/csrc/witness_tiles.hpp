@@ -1,4 +1,4 @@
-// witness_tiles.hpp -- single-tile column kernels of the witness map: a column (or a tile of it) lives in one LDS tile (witness.hip)
+// witness_tiles.hpp -- single-tile column kernels of the witness map: a column (or a tile of it) lives in one LDS tile (witness_lds.hip)
 #pragma once
 #include "witness_cols.hpp"
 

@@ -1,4 +1,4 @@
-// witness_tree_wide.hpp -- the product tree on 2^13 / 2^14 tiles in the wide form: 32 coefficients per thread (witness.hip)
+// witness_tree_wide.hpp -- the product tree on 2^13 / 2^14 tiles in the wide form: 32 coefficients per thread (witness_lds.hip)
 #pragma once
 #include "witness_cols.hpp"
 

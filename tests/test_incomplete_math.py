@@ -20,7 +20,7 @@ def _bitrev(i, l):
 
 
 def _table(p, logmax):
-    """tw[M + i] = w_{2M}^{bitrev(i)}: the device's cyclic table (witness.hip make_cyc) for transforms of up to 2^logmax points"""
+    """tw[M + i] = w_{2M}^{bitrev(i)}: the device's cyclic table (witness_plan.hip make_cyc) for transforms of up to 2^logmax points"""
     n = 1 << logmax
     g = 2
     while True:

@@ -71,7 +71,7 @@ def test_witness_map_at_2_17_and_2_18(m, zk, force):
 @pytest.mark.parametrize("m,force", [(400000, 14), (1048576, 0)])
 def test_two_level_transform_across_blocks_at_2_19_and_2_20(m, force):
     """Y = 128 and 256 blocks (bc2_yfwd_big_kernel<., 2 | 3>).  2^20 constraints is the limit the plan accepts
-    (witness.hip build_plan); toy44's primes (= 1 mod 2^20) have no 2^21-th root, so that size takes the block path unforced."""
+    (witness_plan.hip build_plan); toy44's primes (= 1 mod 2^20) have no 2^21-th root, so that size takes the block path unforced."""
     prm = P.preset("toy44")
     dev, cs, asg, ds, w, names = _run(prm, m, False, force, want=("A_mid", "B_mid", "H"), inc=0)
     assert "bc2_yfwd_big_kernel" in names and "bc2_yinv_a_kernel" in names and "bc2_yinv_b_kernel" in names, names

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / spill table from hipcc's kernel-resource-usage remarks.
-usage: tools/kernel_resources.py ringsnark_amd/csrc/witness.hip [name-filter]"""
+usage: tools/kernel_resources.py ringsnark_amd/csrc/witness_big.hip [name-filter]   (any unit of csrc/)"""
 import re
 import subprocess
 import sys
