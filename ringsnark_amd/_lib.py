@@ -51,6 +51,11 @@ class Peaks(C.Structure):
                 ("hbm_read_gbs", C.c_double), ("hbm_inplace_gbs", C.c_double)]
 
 
+class R1csReport(C.Structure):
+    _fields_ = [("n_violated", C.c_uint64), ("first_row", C.c_uint64), ("first_limb", C.c_uint32), ("first_slot", C.c_uint32),
+                ("a", C.c_uint64), ("b", C.c_uint64), ("c", C.c_uint64)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int), ("total_ms", C.c_float), ("alg_bytes", C.c_double),
                 ("fp64_ops", C.c_double)]
@@ -127,6 +132,10 @@ TUNING_SIGNATURES = {  # every function of include/ringsnark_amd/tuning.h
     "rs_tuning_key": (C.c_char_p, [C.c_int]),
 }
 
+CHECK_SIGNATURES = {  # every function of include/ringsnark_amd/r1cs_check.h
+    "rs_r1cs_check": (C.c_int, [vp, vp, vp, vp, C.POINTER(R1csReport), vp]),
+}
+
 _lib = None
 
 
@@ -140,7 +149,7 @@ def load():
             "ringsnark_amd/librs_hip.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
             "the HIP library is the only implementation, there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -192,14 +201,14 @@ def tuning_from_env(name="RS_TUNING"):
 
 def source_hash():
     """sha256 (first 16 hex digits) over the sources the device library is built from: ringsnark_amd/csrc/*.{hip,hpp},
-    csrc/Makefile, include/ringsnark_amd.h and include/ringsnark_amd/tuning.h.  profiles/*_pmc_*.json carry it, so that bench.py can tell whether a
+    csrc/Makefile, include/ringsnark_amd.h, include/ringsnark_amd/tuning.h and include/ringsnark_amd/r1cs_check.h.  profiles/*_pmc_*.json carry it, so that bench.py can tell whether a
     committed counter file was collected on the kernels it is running (round-3 verdict: nothing tied the two)."""
     import glob
     import hashlib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     files = sorted(glob.glob(os.path.join(root, "ringsnark_amd", "csrc", "*.hip")) + glob.glob(os.path.join(root, "ringsnark_amd", "csrc", "*.hpp")))
     files += [os.path.join(root, "ringsnark_amd", "csrc", "Makefile"), os.path.join(root, "include", "ringsnark_amd.h"),
-              os.path.join(root, "include", "ringsnark_amd", "tuning.h")]
+              os.path.join(root, "include", "ringsnark_amd", "tuning.h"), os.path.join(root, "include", "ringsnark_amd", "r1cs_check.h")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode())

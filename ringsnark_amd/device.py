@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .params import RingParams
-from .r1cs import R1CS
+from .r1cs import R1CS, R1csCheck
 
 
 def to_device(a: np.ndarray, device) -> torch.Tensor:
@@ -336,6 +336,25 @@ class Device:
         _lib.check(self.lib.rs_r1cs_evaluate(self.h, dcs.h, which, mode, _ptr(assignment), _ptr(out), self.stream()))
         return out
 
+    def r1cs_check(self, dcs, assignment, want_flags=False):
+        """r1cs_constraint_system::is_satisfied on the device (rs_r1cs_check): one fused pass over the FULL assignment
+        [n_vars][L][N].  Returns an R1csCheck (satisfied, n_violated, first_row, first_limb, first_slot, a, b, c);
+        want_flags: .flags is a uint8 tensor [m], 1 = constraint violated in some slot."""
+        assert self._count(assignment, self.ring_words) == dcs.n_vars, "the check reads every row of the assignment"
+        flags = torch.empty(dcs.m, dtype=torch.uint8, device=self.device) if want_flags else None
+        rep = _lib.R1csReport()
+        _lib.check(self.lib.rs_r1cs_check(self.h, dcs.h, _ptr(assignment), None if flags is None else C.c_void_p(flags.data_ptr()),
+                                          C.byref(rep), self.stream()))
+        return R1csCheck(int(rep.n_violated), int(rep.first_row), int(rep.first_limb), int(rep.first_slot), int(rep.a), int(rep.b),
+                         int(rep.c), flags)
+
+    def _require_satisfied(self, dcs, assignment):
+        r = self.r1cs_check(dcs, assignment)
+        if not r.satisfied:
+            raise ValueError("assignment does not satisfy the constraint system: %d of %d constraints violated, first constraint %d "
+                             "at limb %d, slot %d (a = %d, b = %d, c = %d)"
+                             % (r.n_violated, dcs.m, r.first_row, r.first_limb, r.first_slot, r.a, r.b, r.c))
+
     def interpolate(self, y):
         n = self._count(y, self.ring_words)
         out = torch.empty_like(y)
@@ -431,11 +450,15 @@ class Device:
         assert k.shape == (n,), (k.shape, n)
         return k, k.ctypes.data_as(_lib.u8p)
 
-    def groth16_prove(self, dcs, pk, assignment, want_empty=True, window=0, kinds=None):
+    def groth16_prove(self, dcs, pk, assignment, want_empty=True, window=0, kinds=None, check=False):
         """pk: dict s_pows, delta_ts, delta_mid, alpha, beta (CUDA tensors).  window != 0: the key vectors hold
         `window` elements each, element t read from t % window (tiled synthetic key, ringsnark_amd.h).
         Key VECTORS given as HostWords: a host-resident key, streamed tile by tile (rs_groth16_pk.host_key).
-        kinds [n_vars]: RS_KIND_ONE for assignment wires held as RingElem Scalar 1 (rs_groth16_prove_kinds)."""
+        kinds [n_vars]: RS_KIND_ONE for assignment wires held as RingElem Scalar 1 (rs_groth16_prove_kinds).
+        check: test the reference's precondition first (r1cs_check; groth16.tcc:74) and raise ValueError, naming the first
+        violated constraint, limb and slot, for an assignment that does not satisfy the system."""
+        if check:
+            self._require_satisfied(dcs, assignment)
         host_key = isinstance(pk["s_pows"], HostWords)
         addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
         assert all(isinstance(pk[k], HostWords) == host_key for k in ("s_pows", "delta_ts") + (("delta_mid",) if pk.get("delta_mid") is not None else ()))
@@ -448,7 +471,10 @@ class Device:
                                                    empty if want_empty else None, self.stream()))
         return proof, [int(e) for e in empty]
 
-    def rinocchio_prove(self, dcs, pk, assignment, d1=None, d2=None, d3=None, window=0, kinds=None):
+    def rinocchio_prove(self, dcs, pk, assignment, d1=None, d2=None, d3=None, window=0, kinds=None, check=False):
+        """check: as in groth16_prove (the reference asserts satisfaction at r1cs_to_qrp.tcc:156)."""
+        if check:
+            self._require_satisfied(dcs, assignment)
         host_key = isinstance(pk.get("s_pows"), HostWords)
         g = lambda k: None if pk.get(k) is None else (pk[k].ptr if isinstance(pk[k], HostWords) else pk[k].data_ptr())
         s = _lib.RinocchioPK(g("s_pows"), g("alpha_s_pows"), g("beta_prods"), g("beta_rv_ts"), g("beta_rw_ts"), g("beta_ry_ts"),

@@ -60,6 +60,57 @@ def from_rows(m, n_vars, n_inputs, rows: Dict[str, List[List[Tuple[int, object]]
     return R1CS(m, n_vars, n_inputs, mats, pidx, np.stack(table))
 
 
+@dataclass
+class R1csCheck:
+    """What a satisfaction check reports (rs_r1cs_report of ringsnark_amd/r1cs_check.h, field for field)."""
+    n_violated: int  # constraints violated in at least one (limb, slot)
+    first_row: int  # lowest violated constraint; m when there is none
+    first_limb: int  # with first_slot: the lowest ring-layout index limb*N + slot that violates first_row
+    first_slot: int
+    a: int  # canonical residues of the three evaluations there; 0 when there is none
+    b: int
+    c: int
+    flags: object = None  # uint8 [m], 1 = violated (numpy on the host, a torch tensor from the device), or None
+
+    @property
+    def satisfied(self):
+        return self.n_violated == 0
+
+
+def is_satisfied(cs: R1CS, assignment, q: List[int]) -> R1csCheck:
+    """r1cs_constraint_system::is_satisfied (relations/constraint_satisfaction_problems/r1cs/r1cs.tcc:122-158) on the
+    host, exact (Python integers): <a,(1,x)> * <b,(1,x)> == <c,(1,x)> for every constraint, limb and slot, and where it
+    first fails.  assignment: [n_vars][L][N] canonical residues (all n_vars rows).  The host mirror of the device check."""
+    asg = np.asarray(assignment)
+    L = len(q)
+    assert asg.ndim == 3 and asg.shape[0] == cs.n_vars and asg.shape[1] == L, asg.shape
+    N = asg.shape[2]
+    x = asg.astype(object)
+    ev = np.zeros((3, cs.m, L, N), dtype=object)
+    for k, name in enumerate("abc"):
+        rp, col, coeff = cs.mats[name]
+        pidx = None if cs.poly_idx is None else cs.poly_idx[name]
+        for i in range(cs.m):
+            for e in range(int(rp[i]), int(rp[i + 1])):
+                for l in range(L):
+                    if pidx is not None and pidx[e] >= 0:
+                        cf = cs.poly_table[int(pidx[e]), l].astype(object)
+                    else:
+                        cf = int(coeff[l, e])
+                    v = 1 if col[e] == 0 else x[int(col[e]) - 1, l]
+                    ev[k, i, l] = (ev[k, i, l] + cf * v) % int(q[l])
+    qs = np.array([int(p) for p in q], dtype=object).reshape(1, L, 1)
+    bad = ((ev[0] * ev[1]) % qs != ev[2]).reshape(cs.m, L * N)
+    flags = bad.any(axis=1).astype(np.uint8)
+    n = int(flags.sum())
+    if n == 0:
+        return R1csCheck(0, cs.m, 0, 0, 0, 0, 0, flags)
+    row = int(np.argmax(flags))
+    idx = int(np.argmax(bad[row]))
+    limb, slot = idx // N, idx % N
+    return R1csCheck(n, row, limb, slot, int(ev[0, row, limb, slot]), int(ev[1, row, limb, slot]), int(ev[2, row, limb, slot]), flags)
+
+
 def chain_r1cs(m: int, q: List[int]) -> R1CS:
     """x_i * x_{i+1} = x_{i+2}, i < m; variables x_0..x_{m+1}; x_0, x_1 public (n_aux = m)."""
     rows = {"a": [[(i + 1, 1)] for i in range(m)], "b": [[(i + 2, 1)] for i in range(m)], "c": [[(i + 3, 1)] for i in range(m)]}
