@@ -56,6 +56,11 @@ class R1csReport(C.Structure):
                 ("a", C.c_uint64), ("b", C.c_uint64), ("c", C.c_uint64)]
 
 
+class VerifyReport(C.Structure):
+    _fields_ = [("accepted", C.c_uint32), ("failed", C.c_uint32), ("n_bad", C.c_uint64 * 6), ("first_check", C.c_uint32),
+                ("first_limb", C.c_uint32), ("first_slot", C.c_uint32), ("lhs", C.c_uint64), ("rhs", C.c_uint64)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int), ("total_ms", C.c_float), ("alg_bytes", C.c_double),
                 ("fp64_ops", C.c_double)]
@@ -136,6 +141,16 @@ CHECK_SIGNATURES = {  # every function of include/ringsnark_amd/r1cs_check.h
     "rs_r1cs_check": (C.c_int, [vp, vp, vp, vp, C.POINTER(R1csReport), vp]),
 }
 
+VERIFY_SIGNATURES = {  # every function of include/ringsnark_amd/verify.h
+    "rs_io_eval_at": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "rs_groth16_vk_create": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
+    "rs_groth16_vk_destroy": (None, [vp]),
+    "rs_rinocchio_vk_create": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
+    "rs_rinocchio_vk_destroy": (None, [vp]),
+    "rs_groth16_verify": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(VerifyReport), vp]),
+    "rs_rinocchio_verify": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(VerifyReport), vp]),
+}
+
 _lib = None
 
 
@@ -149,7 +164,7 @@ def load():
             "ringsnark_amd/librs_hip.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
             "the HIP library is the only implementation, there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **VERIFY_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

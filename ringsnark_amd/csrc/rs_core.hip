@@ -793,7 +793,7 @@ using namespace rs;
 extern "C" {
 
 const char *rs_last_error(void) { return g_last_error.c_str(); }
-int rs_version(void) { return 102; }  // 102: rs_r1cs_check; 101: rs_msm_vec::slot_const (struct must be zero-initialised), rs_enc_noise_budget, RS_ERR_NOISE
+int rs_version(void) { return 103; }  // 103: verify.h (rs_io_eval_at, verifiers); 102: rs_r1cs_check; 101: rs_msm_vec::slot_const (struct must be zero-initialised), rs_enc_noise_budget, RS_ERR_NOISE
 
 int rs_ctx_create(int device, int N, int L, const uint64_t *q, int N_enc, int K, const uint64_t *Q, rs_ctx **out) {
   RS_API_BEGIN

@@ -4,6 +4,7 @@ PyTorch is used for what it is good at here -- device memory, streams, torch.dis
 nothing else: every arithmetic operation goes through librs_hip.so.  Residues live in int64 CUDA
 tensors (bit-identical to the uint64 boundary layout; all values are < 2^50).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -95,6 +96,32 @@ class DeviceR1CS:
         if getattr(self, "h", None) and self.dev.lib is not None:
             self.dev.lib.rs_r1cs_destroy(self.h)
             self.h = None
+
+
+IO_EVAL_TILE = 64  # rows per tile of rs_io_eval_at (csrc/verify.hip IO_TILE): its workspace is 2 * ceil(m / 64) ring elements
+
+
+class VerifyResult(collections.namedtuple("VerifyResult", "accepted failed n_bad first_check first_limb first_slot lhs rhs")):
+    """rs_verify_report (ringsnark_amd/verify.h), field for field; n_bad is a tuple of six counts."""
+    __slots__ = ()
+
+    def __bool__(self):
+        return bool(self.accepted)
+
+
+class DeviceVK:
+    """A verification key on the device (rs_groth16_vk / rs_rinocchio_vk): the public columns of the instance map at s,
+    Z(s), the trapdoor elements and the secret key.  close() (or garbage collection) zeroes and frees it."""
+
+    def __init__(self, dev, scheme, handle, n_inputs):
+        self.dev, self.scheme, self.h, self.n_inputs = dev, scheme, handle, n_inputs
+
+    def close(self):
+        if getattr(self, "h", None) and self.dev.lib is not None:
+            (self.dev.lib.rs_groth16_vk_destroy if self.scheme == "groth16" else self.dev.lib.rs_rinocchio_vk_destroy)(self.h)
+        self.h = None
+
+    __del__ = close
 
 
 class Device:
@@ -227,6 +254,54 @@ class Device:
         _lib.check(self.lib.rs_instance_map_eval(self.h, dcs.h, _ptr(s), _ptr(At), _ptr(Bt), _ptr(Ct), _ptr(Ht), _ptr(Zt),
                                                  self.stream()))
         return At, Bt, Ct, Ht, Zt
+
+    # ---- verifiers (ringsnark_amd/verify.h)
+    def io_eval_at(self, dcs, s):
+        """rs_io_eval_at: (Aio, Bio, Cio [n_inputs+1][L][N], Zt [L][N]) -- rows 0..n_inputs of instance_map_eval's At, Bt, Ct
+        and its Zt, bit for bit, without the [m][L][N] Lagrange values or the [n_vars+1][L][N] outputs."""
+        n1 = dcs.n_inputs + 1
+        A, B, Cc, Zt = self.ring_empty(n1), self.ring_empty(n1), self.ring_empty(n1), self.ring_empty()
+        _lib.check(self.lib.rs_io_eval_at(self.h, dcs.h, _ptr(s), _ptr(A), _ptr(B), _ptr(Cc), _ptr(Zt), self.stream()))
+        return A, B, Cc, Zt
+
+    def _vk_part(self, v):
+        return v if isinstance(v, torch.Tensor) else self.put(v)
+
+    def groth16_vk(self, dcs, vk):
+        """vk: dict s, alpha, beta, gamma, delta ([L][N]) and sk ([K][N_enc], NTT form), numpy or device tensors -- what
+        tests/snark_ref.py's generator returns.  RsError(RS_ERR_NOT_INVERTIBLE) unless gamma is a unit (groth16.tcc:162)."""
+        t = [self._vk_part(vk[k]) for k in ("s", "alpha", "beta", "gamma", "delta", "sk")]
+        self.sync()
+        h = C.c_void_p()
+        _lib.check(self.lib.rs_groth16_vk_create(self.h, dcs.h, *[_ptr(x) for x in t], C.byref(h)))
+        return DeviceVK(self, "groth16", h, dcs.n_inputs)
+
+    def rinocchio_vk(self, dcs, vk):
+        """vk: dict s, alpha, beta, r_v, r_w, r_y and sk."""
+        t = [self._vk_part(vk[k]) for k in ("s", "alpha", "beta", "r_v", "r_w", "r_y", "sk")]
+        self.sync()
+        h = C.c_void_p()
+        _lib.check(self.lib.rs_rinocchio_vk_create(self.h, dcs.h, *[_ptr(x) for x in t], C.byref(h)))
+        return DeviceVK(self, "rinocchio", h, dcs.n_inputs)
+
+    def _verify(self, fn, vk, scheme, n_elems, primary, proof, empty):
+        assert vk.scheme == scheme and vk.h, "not a live %s verification key" % scheme
+        assert self._count(proof, self.enc_words) == n_elems
+        assert vk.n_inputs == 0 or self._count(primary, self.ring_words) == vk.n_inputs
+        em = None if empty is None else (C.c_int * n_elems)(*[int(e) for e in empty])
+        rep = _lib.VerifyReport()
+        _lib.check(fn(self.h, vk.h, _ptr(primary) if vk.n_inputs else None, _ptr(proof), em, C.byref(rep), self.stream()))
+        return VerifyResult(bool(rep.accepted), int(rep.failed), tuple(int(x) for x in rep.n_bad), int(rep.first_check),
+                            int(rep.first_limb), int(rep.first_slot), int(rep.lhs), int(rep.rhs))
+
+    def groth16_verify(self, vk, primary, proof, empty=None):
+        """groth16::verifier (groth16.tcc:117-170): primary [n_inputs][L][N], proof [3] encoding elements, empty: the flags
+        the prover returned.  A VerifyResult (truthy when accepted); RsError(RS_ERR_NOISE) for a proof past its noise budget."""
+        return self._verify(self.lib.rs_groth16_verify, vk, "groth16", 3, primary, proof, empty)
+
+    def rinocchio_verify(self, vk, primary, proof, empty=None):
+        """rinocchio::verifier (rinocchio.tcc:192-295): proof [9]; failed bit c = check c of verify.h (V', W', Y', H', L_beta, P)."""
+        return self._verify(self.lib.rs_rinocchio_verify, vk, "rinocchio", 9, primary, proof, empty)
 
     # ---- 8(f) f4
     def enc_serialize(self, enc, empty=None):
