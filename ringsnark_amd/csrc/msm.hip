@@ -117,34 +117,6 @@ static void launch_mac_v2(rs_ctx *ctx, const MacArgs2 &a, const MsmScratch &sc, 
   const size_t lds = (padded_len((size_t)ctx->N_enc) + (size_t)ctx->N_enc) * sizeof(double);
   const int rows = a.n_chunks * ctx->L;
   const unsigned blocks = (unsigned)(((rows + 7) / 8) * 8 * ctx->K);
-  if (g_tune.mac_variant == 3 && ctx->logN_enc == 13) {  // 16 waves of 128 VGPRs (4 waves per SIMD), plaintext row not prefetched
-    set_max_dyn_lds((const void *)mac_kernel_v2<1024, 13>, (int)lds);
-    hipLaunchKernelGGL((mac_kernel_v2<1024, 13>), dim3(blocks), dim3(1024), lds, st, a, ctx->L, ctx->K, ctx->logN_enc, sc.coeff<Mod>());
-    RS_HIP(hipGetLastError());
-    return;
-  }
-  if (ctx->logN_enc == 13 && g_tune.mac_variant != 4) {
-#define RS_MAC_LAUNCH(AB)                                                                                             \
-  do {                                                                                                                \
-    set_max_dyn_lds((const void *)mac_kernel_v2<512, 13, AB>, \
-                               (int)lds);                                                                           \
-    hipLaunchKernelGGL((mac_kernel_v2<512, 13, AB>), dim3(blocks), dim3(512), lds, st, a, ctx->L, ctx->K,             \
-                       ctx->logN_enc, sc.coeff<Mod>());                                                               \
-  } while (0)
-#ifdef RS_EXPERIMENTS  // timing-only ablations (wrong results): never part of the release library
-    switch (g_tune.mac_ablate) {
-      case 1: RS_MAC_LAUNCH(1); break;
-      case 2: RS_MAC_LAUNCH(2); break;
-      case 6: RS_MAC_LAUNCH(6); break;
-      default: RS_MAC_LAUNCH(0); break;
-    }
-#else
-    RS_MAC_LAUNCH(0);
-#endif
-#undef RS_MAC_LAUNCH
-    RS_HIP(hipGetLastError());
-    return;
-  }
   set_max_dyn_lds((const void *)mac_kernel_v2<512>, (int)lds);
   hipLaunchKernelGGL(mac_kernel_v2<512>, dim3(blocks), dim3(512), lds, st, a, ctx->L, ctx->K, ctx->logN_enc, sc.coeff<Mod>());
   RS_HIP(hipGetLastError());
@@ -182,22 +154,6 @@ static void launch_mac_v3(rs_ctx *ctx, const MacArgs3 &a, const MsmScratch &sc, 
   } else {
     set_max_dyn_lds((const void *)mac_kernel_v3<false>, (int)lds);
     hipLaunchKernelGGL(mac_kernel_v3<false>, dim3(blocks), dim3(256), lds, st, a, ctx->L, ctx->K, tabs);
-  }
-  RS_HIP(hipGetLastError());
-}
-
-// mac_kernel_v4 with ONE key vector (mac_variant 6, N_enc = 8192): two 512-thread workgroups per CU at <= 128 VGPRs
-static void launch_mac_v4_one(rs_ctx *ctx, const MacArgs4 &a, bool paired, const MsmScratch &sc, hipStream_t st) {
-  const size_t lds = (size_t)2 * (4096 + 512) * sizeof(double);  // two tiles
-  const unsigned rows = (unsigned)ctx->L * (unsigned)a.n_chunks;
-  const NttTable *tabs = ctx->use_int ? static_cast<const NttTable *>(sc.d_coeff_tabs_f64) : sc.coeff<Mod>();
-  const unsigned blocks = ((rows + 7) / 8) * 8 * 2u * (unsigned)ctx->K * (unsigned)a.n_groups;
-  if (paired) {
-    set_max_dyn_lds((const void *)mac_kernel_v4<13, true, 1>, (int)lds);
-    hipLaunchKernelGGL((mac_kernel_v4<13, true, 1>), dim3(blocks), dim3(512), lds, st, a, ctx->L, ctx->K, tabs);
-  } else {
-    set_max_dyn_lds((const void *)mac_kernel_v4<13, false, 1>, (int)lds);
-    hipLaunchKernelGGL((mac_kernel_v4<13, false, 1>), dim3(blocks), dim3(512), lds, st, a, ctx->L, ctx->K, tabs);
   }
   RS_HIP(hipGetLastError());
 }
@@ -420,7 +376,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   (void)plain13;
   bool v3 = false, plain_wide = false, hybrid = false;
   if constexpr (FP) {
-    v3 = g_tune.mac_variant >= 5 && (n == 8192 || n == 16384);  // 6: one-key launches in the 512-thread shape (mac_kernel_v4<13, ., 1>)
+    v3 = g_tune.mac_variant >= 5 && (n == 8192 || n == 16384);
     plain_wide = g_tune.plain_variant == 1 && n == 8192 && (ctx->N == 8192 || ctx->N == 4096);
   } else {
     // Hybrid context: ring primes beyond 2^50 (SEAL's 54-bit BFVDefault(2048) prime of the reference's logistic-regression
@@ -589,40 +545,6 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
                            terms * L * K * (ntt_fp64(nd, logn_d) + 8.0 * nd / 2.0 + 2.0 * 15.0 * nd));
             launch_mac_v4(ctx, a4, paired, sc, st);
           }
-        } else if (g_tune.mac_variant == 6 && n == 8192) {
-          // one key vector per launch in the 512-thread shape of mac_kernel_v4 (four waves per SIMD), two groups that read it
-          // as neighbouring workgroups of an XCD (A and B against s_pows, groth16.tcc:89-103)
-          for (int c = 0; c < n_crs; c++)
-            for (int g0 = 0; g0 < n_groups; g0 += 2) {
-              const int ng = std::min(2, n_groups - g0);
-              MacArgs4 a4;
-              memset(&a4, 0, sizeof(a4));
-              unsigned long long tmax = 0;
-              double terms = 0;
-              for (int gi = 0; gi < ng; gi++) {
-                a4.C[gi] = reinterpret_cast<const double *>(Cptr(g0 + gi));
-                a4.terms[gi] = group_terms(g0 + gi);
-                a4.partial[0][gi] = d_partial + (size_t)(c * n_groups + g0 + gi) * enc_words;
-                tmax = std::max(tmax, a4.terms[gi]);
-                terms += (double)a4.terms[gi];
-              }
-              a4.crs[0] = crs_at(c, t0);
-              a4.part_stride = (size_t)n_sets * enc_words;
-              a4.n_groups = ng;
-              a4.n_chunks = base.n_chunks;
-              a4.terms_per_chunk = base.terms_per_chunk;
-              a4.accumulate = base.accumulate;
-              a4.acc_period = base.acc_period;
-              for (int jj = 0; jj < K; jj++) {
-                double end = 0;
-                a4.red_mask[jj] = fwd_reduce_mask_from(ctx->Q[jj], ctx->logN_enc, b0, &end);
-                if (end > 562949953421312.0) a4.reduce_u = 1;
-              }
-              ProfScope prof(ctx, st, paired ? "mac_kernel_v4<13, true, 1>" : "mac_kernel_v4<13, false, 1>",
-                             (double)tmax * (double)enc_words * 8.0 + terms * (double)L * nd * 8.0 + ng * (double)enc_words * 8.0,
-                             terms * L * K * (ntt_fp64(nd, logn_d) + 8.0 * nd / 2.0 + 15.0 * nd));
-              launch_mac_v4_one(ctx, a4, paired, sc, st);
-            }
         } else
         // chunks: two workgroups per CU in one wave of workgroups (512), shared by the groups of a launch
         for (int c = 0; c < n_crs; c++)
@@ -678,7 +600,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
         // every ciphertext word of the group's terms once, every plaintext row once (shared by the K
         // prime workgroups through L2), the accumulator set written once
         const double terms = (double)a2.terms;
-        ProfScope prof(ctx, st, (g_tune.mac_variant == 3 && ctx->logN_enc == 13) ? "mac_kernel_v2<1024, 13, 0>" : "mac_kernel_v2", terms * ((double)enc_words * 8.0 + (double)L * nd * 8.0) + (double)enc_words * 8.0,
+        ProfScope prof(ctx, st, "mac_kernel_v2", terms * ((double)enc_words * 8.0 + (double)L * nd * 8.0) + (double)enc_words * 8.0,
                        terms * L * K * (ntt_fp64(nd, logn_d) + 15.0 * nd));
         launch_mac_v2(ctx, a2, sc, st);
       }

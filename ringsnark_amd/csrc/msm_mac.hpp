@@ -160,13 +160,9 @@ struct MacArgs2 {
   int terms_per_chunk, n_chunks;
   int accumulate, acc_period, reduce_u;
 };
-// THREADS = 1024 (default at N_enc = 8192): 16 waves, 118 VGPRs, four waves per SIMD, the plaintext
-// row loaded where it is used.  THREADS = 512: 8 waves, ~240 VGPRs, the plaintext row of term t+1
-// prefetched as well.  Both use radix-8 private rounds (RS_MAC_MAXR) to stay free of scratch.
-// LOGN_CT != 0: transform length fixed at compile time (rounds specialised).  ABLATE (experiments,
-// tools/mac_ablate.py): 1 = skip the transform, 2 = skip the ciphertext loads, 4 = skip the C loads;
-// a compile-time parameter because a run-time branch around each load makes the compiler wait for
-// every load right where it is issued.
+// The one instantiation is <512> (8 waves, ~240 VGPRs, the plaintext row of term t+1 prefetched as well; radix-8 private
+// rounds, RS_MAC_MAXR, keep it free of scratch) with the run-time length.  The 1024-thread shape, the compile-time length
+// (LOGN_CT != 0) and the timing ablations (ABLATE != 0) are retired; their parameters stay until a change of the symbol.
 template <int THREADS, int LOGN_CT = 0, int ABLATE = 0>
 __global__ void __launch_bounds__(THREADS)
 mac_kernel_v2(MacArgs2 a, int L, int K, int logn_arg, const NttTable *__restrict__ coeff_tabs) {
@@ -659,11 +655,7 @@ struct MacArgs4 {
 };
 // LOGN = 13 (N_enc = 8192): the workgroup owns HALF of the spectrum and folds one stage while the row is loaded (PAIRED:
 // rows in plain_center_wide_kernel's paired layout, one 16-byte load per operand pair).
-// NKEY = 1 (round 6; N_enc = 8192): ONE key vector in the same shape -- half the accumulators and half the ciphertext registers,
-// so the kernel fits 128 VGPRs and TWO 512-thread workgroups share a CU: four waves per SIMD instead of mac_kernel_v3's two
-// (256 threads x 16 points, 240 VGPRs), the latency of the tile exchanges and of the one workgroup barrier per term hidden by
-// twice the waves.  Same arithmetic per coefficient as mac_kernel_v3 (stage 0 folded into the row load, 12 stages, the
-// multiply-accumulate one term behind): bit-identical results (mac_variant 6 / 5).
+// NKEY = 1 (one key vector in the same shape, four waves per SIMD) is retired: only NKEY = 2 is instantiated.
 template <int LOGN, bool PAIRED, int NKEY = 2>
 __global__ void __launch_bounds__(512, (NKEY == 1 ? 4 : 2))
 mac_kernel_v4(MacArgs4 a, int L, int K, const NttTable *__restrict__ coeff_tabs) {

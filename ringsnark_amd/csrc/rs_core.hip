@@ -311,100 +311,6 @@ static void launch_ntt_wp(const NttTable &t, uint64_t *d_data, size_t batch, hip
 }
 
 
-// Persistent, software-pipelined forward transform (the streaming form of ntt_kernel_wp): one
-// workgroup per CU loops over polynomials of one prime.  The twiddle table lives in LDS next to
-// the tile, so the loop's only vector-memory traffic is the data itself, and the NEXT polynomial is
-// loaded into registers (in the first round's radix-4 access pattern) while the current one is
-// transformed.  1024 threads: two cross-wave radix-4 rounds, then nine wave-private stages per
-// 512-point block, then each wave streams its block out.
-template <int G>  // radix-4 groups per thread in the first round: n / 4096
-__global__ void __launch_bounds__(1024)
-ntt_fwd_stream_kernel(uint64_t *__restrict__ data, unsigned long long batch, int logn, const double *__restrict__ tw, Mod mod,
-                      uint32_t red_mask) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *s = reinterpret_cast<double *>(smem);
-  const int n = 1 << logn;
-  double *twl = s + padded_len((size_t)n);
-  for (int i = threadIdx.x; i < n; i += 1024) twl[i] = tw[i];
-  const int q = n >> 2;  // gap of the first radix-4 round
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int logb = logn - 4, off = wave << logb;
-  const LdsIO lds{s};
-  const LdsBlockIO blk{s + pidx(off)};
-  const Lanes wl = wave_lanes(true);
-  uint64_t pre[G][4];
-  // The finished polynomial leaves through registers ONE ITERATION LATE: its stores are issued after the next
-  // polynomial's first round has consumed the prefetched loads.  gfx9-family counters track loads and stores in
-  // one vmcnt and they complete out of order with respect to each other, so waiting for a load that was issued
-  // before stores means vmcnt(0), i.e. draining those stores; issued in this order the only stores in flight at
-  // the wait are a whole transform old.
-  constexpr int NOUT = 2 * G;  // 16-byte pairs per lane of a wave block: (n / 16) / 2 / 64
-  ulonglong2 outr[NOUT];
-  unsigned long long p_out = ~0ull;
-  unsigned long long p = blockIdx.x;
-  if (p < batch) {
-    const uint64_t *src = data + p * (size_t)n;
-#pragma unroll
-    for (int g = 0; g < G; g++)
-#pragma unroll
-      for (int e = 0; e < 4; e++) pre[g][e] = src[threadIdx.x + g * 1024 + e * q];
-  }
-  __syncthreads();
-  const double w1 = twl[1], w2 = twl[2], w3 = twl[3];
-  for (; p < batch; p += gridDim.x) {
-    // stages 0,1 from registers (root 1: twiddles tw[1]; tw[2], tw[3])
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      const int base = threadIdx.x + g * 1024;
-      double v0 = from_u64(pre[g][0]), v1 = from_u64(pre[g][1]), v2 = from_u64(pre[g][2]), v3 = from_u64(pre[g][3]);
-      double t = mulmod(v2, w1, mod), u = mulmod(v3, w1, mod);
-      double a0 = v0 + t, a2 = v0 - t, a1 = v1 + u, a3 = v1 - u;
-      t = mulmod(a1, w2, mod);
-      u = mulmod(a3, w3, mod);
-      const int pb = pidx(base);  // base < q: the quarter offsets occupy disjoint bits
-      s[pb] = a0 + t;
-      s[pcomb(pb, pidx(q))] = a0 - t;
-      s[pcomb(pb, pidx(2 * q))] = a2 + u;
-      s[pcomb(pb, pidx(3 * q))] = a2 - u;
-    }
-    __syncthreads();
-    if (p_out != ~0ull) {  // the previous polynomial, held in registers since the end of the last iteration
-      ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(data + p_out * (size_t)n + off);
-#pragma unroll
-      for (int k = 0; k < NOUT; k++) dst[lane + 64 * k] = outr[k];
-    }
-    const unsigned long long pn = p + gridDim.x;
-    if (pn < batch) {
-      const uint64_t *src = data + pn * (size_t)n;
-#pragma unroll
-      for (int g = 0; g < G; g++)
-#pragma unroll
-        for (int e = 0; e < 4; e++) pre[g][e] = src[threadIdx.x + g * 1024 + e * q];
-    }
-    fwd_round<2>(lds, lds, logn, logn, 2, twl, 1, mod, red_mask, Lanes{(int)threadIdx.x, 1024, true});
-    __syncthreads();
-    for (int st = 0; st < logb;) {
-      const int R = pick_radix(logb - st, 3);
-      fwd_round_dispatch<3>(R, blk, blk, logb, logb, st, twl, 16 + wave, mod, red_mask >> 4, wl);
-      wave_sync();
-      st += R;
-    }
-#pragma unroll
-    for (int k = 0; k < NOUT; k++) {
-      const int pi = pidx(off + 2 * (lane + 64 * k));
-      outr[k].x = to_u64(canon(s[pi], mod));
-      outr[k].y = to_u64(canon(s[pnext(pi)], mod));
-    }
-    p_out = p;
-    __syncthreads();
-  }
-  if (p_out != ~0ull) {
-    ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(data + p_out * (size_t)n + off);
-#pragma unroll
-    for (int k = 0; k < NOUT; k++) dst[lane + 64 * k] = outr[k];
-  }
-}
-
 // The transform for ANY arithmetic (used by the integer contexts; the FP64 contexts run the tuned variants above):
 // one workgroup per polynomial, tile in LDS, radix-8 rounds with workgroup barriers.
 template <bool INV, class T, class M>
@@ -488,12 +394,12 @@ void launch_ntt_int(rs_ctx *ctx, const NttTableI &t, uint64_t *d_data, size_t ba
   RS_HIP(hipGetLastError());
 }
 
-template <bool INV, int MAXR, bool DIN, bool DOUT, int THREADS>
-static void launch_ntt_variant(const NttTable &t, uint64_t *d_data, size_t batch, hipStream_t st) {
+template <bool INV>
+static void launch_ntt_barrier(const NttTable &t, uint64_t *d_data, size_t batch, hipStream_t st) {
   const size_t lds = padded_len((size_t)1 << t.logn) * sizeof(double);
   const int n = 1 << t.logn;
-  const int thr = std::max(64, std::min(THREADS, n >> MAXR));
-  auto kern = ntt_kernel<INV, MAXR, DIN, DOUT, THREADS>;
+  const int thr = std::max(64, std::min(1024, n >> 3));
+  auto kern = ntt_kernel<INV, 3, false, false, 1024>;
   set_max_dyn_lds((const void *)kern, (int)lds);
   hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(thr), lds, st, d_data, t.logn, INV ? t.d_itw : t.d_tw, t.mod,
                      t.ninv, INV ? t.inv_red_mask : t.fwd_red_mask);
@@ -519,81 +425,34 @@ static void launch_ntt_wide_shape(const NttTable &t, uint64_t *d_data, size_t ba
   }
   RS_HIP(hipGetLastError());
 }
-static bool launch_ntt_wide(const NttTable &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st) {
+static void launch_ntt_wide(const NttTable &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st) {
   const bool red = (inverse ? t.inv_red_mask : t.fwd_red_mask) != 0;
   if (t.logn == 14)
     red ? launch_ntt_wide_shape<14, true>(t, d_data, batch, inverse, st) : launch_ntt_wide_shape<14, false>(t, d_data, batch, inverse, st);
   else if (t.logn == 13)
     red ? launch_ntt_wide_shape<13, true>(t, d_data, batch, inverse, st) : launch_ntt_wide_shape<13, false>(t, d_data, batch, inverse, st);
-  else if (t.logn == 12)
-    red ? launch_ntt_wide_shape<12, true>(t, d_data, batch, inverse, st) : launch_ntt_wide_shape<12, false>(t, d_data, batch, inverse, st);
   else
-    return false;
-  return true;
+    red ? launch_ntt_wide_shape<12, true>(t, d_data, batch, inverse, st) : launch_ntt_wide_shape<12, false>(t, d_data, batch, inverse, st);
 }
 
+// ntt_variant -- 14: wide kernels (2^12..2^14), else as 8; 8..13: wave-private kernel where the length allows, else as 0;
+// anything else: barrier kernel.
 void launch_ntt(rs_ctx *ctx, const NttTable &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st) {
-  (void)ctx;
   if (batch == 0) return;
-#define RS_NTT_CASE(V, MAXR, DIN_F, DOUT_F, DIN_I, DOUT_I, THR)                         \
-  case V:                                                                              \
-    if (inverse)                                                                       \
-      launch_ntt_variant<true, MAXR, DIN_I, DOUT_I, THR>(t, d_data, batch, st);        \
-    else                                                                               \
-      launch_ntt_variant<false, MAXR, DIN_F, DOUT_F, THR>(t, d_data, batch, st);       \
-    break;
-  if (g_tune.ntt_variant == 14 && launch_ntt_wide(t, d_data, batch, inverse, st)) return;
-  if ((g_tune.ntt_variant == 12 || g_tune.ntt_variant == 14) && !inverse && t.logn >= 12 && t.logn <= 13 && t.fwd_red_mask < 4) {
-    const size_t lds = (padded_len((size_t)1 << t.logn) + ((size_t)1 << t.logn)) * sizeof(double);
-    const unsigned grid = (unsigned)std::min<size_t>(batch, 256);
-    if (t.logn == 13) {
-      set_max_dyn_lds((const void *)ntt_fwd_stream_kernel<2>, (int)lds);
-      hipLaunchKernelGGL(ntt_fwd_stream_kernel<2>, dim3(grid), dim3(1024), lds, st, d_data, (unsigned long long)batch, t.logn,
-                         t.d_tw, t.mod, t.fwd_red_mask);
-    } else {
-      set_max_dyn_lds((const void *)ntt_fwd_stream_kernel<1>, (int)lds);
-      hipLaunchKernelGGL(ntt_fwd_stream_kernel<1>, dim3(grid), dim3(1024), lds, st, d_data, (unsigned long long)batch, t.logn,
-                         t.d_tw, t.mod, t.fwd_red_mask);
-    }
-    RS_HIP(hipGetLastError());
-    return;
-  }
-  const int wp_waves = (g_tune.ntt_variant == 9 || g_tune.ntt_variant == 13) ? 16 : (g_tune.ntt_variant == 10 ? 4 : 8);
-  const bool wp_ok = (1 << t.logn) >= wp_waves * LDS_BLOCK_MIN;  // wave-private blocks need n / W >= LDS_BLOCK_MIN
-  if (wp_ok && g_tune.ntt_variant >= 8 && g_tune.ntt_variant <= 14) {
-    switch (g_tune.ntt_variant) {
-      case 8:
-      case 12:  // streaming forward kernel not applicable (inverse, or shape): wave-private kernel
-      case 14:  // wide kernels not applicable (shape)
-        inverse ? launch_ntt_wp<true, 4, 512>(t, d_data, batch, st) : launch_ntt_wp<false, 4, 512>(t, d_data, batch, st);
-        break;
-      case 9:
-        inverse ? launch_ntt_wp<true, 3, 1024>(t, d_data, batch, st) : launch_ntt_wp<false, 3, 1024>(t, d_data, batch, st);
-        break;
-      case 13:  // radix-8 rounds at 8 waves per SIMD (<= 64 VGPRs), two workgroups per CU
-        inverse ? launch_ntt_wp<true, 3, 1024, 8>(t, d_data, batch, st) : launch_ntt_wp<false, 3, 1024, 8>(t, d_data, batch, st);
-        break;
-      case 10:
-        inverse ? launch_ntt_wp<true, 5, 256>(t, d_data, batch, st) : launch_ntt_wp<false, 5, 256>(t, d_data, batch, st);
-        break;
-      default:
-        inverse ? launch_ntt_wp<true, 3, 512>(t, d_data, batch, st) : launch_ntt_wp<false, 3, 512>(t, d_data, batch, st);
-        break;
-    }
-    return;
-  }
-  switch (g_tune.ntt_variant) {
-    RS_NTT_CASE(1, 4, false, false, false, false, 512)
-    RS_NTT_CASE(2, 4, true, false, false, true, 512)
-    RS_NTT_CASE(3, 4, true, true, true, true, 512)
-    RS_NTT_CASE(4, 5, false, false, false, false, 256)
-    RS_NTT_CASE(5, 5, true, false, false, true, 256)
-    RS_NTT_CASE(6, 5, true, true, true, true, 256)
-    RS_NTT_CASE(7, 3, true, false, false, true, 1024)
-    default:  // 0, and any wave-private request on a transform too short for it
-      RS_NTT_CASE(0, 3, false, false, false, false, 1024)
-  }
-#undef RS_NTT_CASE
+  const int v = g_tune.ntt_variant;
+  const bool wide = v == 14 && t.logn >= 12 && t.logn <= 14;
+  const bool wp = v >= 8 && v <= 14 && (1 << t.logn) >= 8 * LDS_BLOCK_MIN;  // wave-private blocks need n / W >= LDS_BLOCK_MIN
+  std::unique_lock<std::mutex> lk(ctx->mu, std::defer_lock);
+  if (ctx->profiling) lk.lock();  // the record ProfScope appends to belongs to the holder of mu
+  const double n = (double)((size_t)1 << t.logn);
+  ProfScope prof(ctx, st, wide ? (inverse ? "ntt_inv_wide_kernel" : "ntt_fwd_wide_kernel") : wp ? "ntt_kernel_wp" : "ntt_kernel<",
+                 (double)batch * n * 16.0, (double)batch * ntt_fp64(n, t.logn));
+  if (wide)
+    launch_ntt_wide(t, d_data, batch, inverse, st);
+  else if (wp)
+    inverse ? launch_ntt_wp<true, 4, 512>(t, d_data, batch, st) : launch_ntt_wp<false, 4, 512>(t, d_data, batch, st);
+  else
+    inverse ? launch_ntt_barrier<true>(t, d_data, batch, st) : launch_ntt_barrier<false>(t, d_data, batch, st);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -775,11 +634,8 @@ const TuneKnob &tune_knob(const char *key) {
   throw Error(RS_ERR_INVALID, std::string("unknown tuning key ") + key);
 }
 void tune_check_force_bc(int value) { RS_REQUIRE(value == 0 || (value >= 5 && value <= 20), "witness_force_bc must be 0 or in [5, 20]"); }
-void tune_check_sub_ct(int value) {
-  (void)value;
-#ifndef RS_EXPERIMENTS  // the superseded A/B variants 1 (sub_ntt_ct_kernel) and 3 (sub_ntt_wide16_kernel) are not compiled in
+void tune_check_sub_ct(int value) {  // 1 and 3 selected kernels that are gone; the message is the one callers have always seen
   if (value != 0 && value != 2) throw Error(RS_ERR_UNSUPPORTED, "witness_sub_ct 1 and 3 exist in the experiments build only");
-#endif
 }
 }  // namespace
 

@@ -2,20 +2,20 @@
 // written.  struct Tuning, the table behind rs_set_tuning / rs_get_tuning / rs_tuning_key (rs_core.hip) and every list of
 // knobs outside the library derive from the rows below.  Contract: one process-wide instance (rs::g_tune), host variables
 // only; a set takes effect at the next launch / plan build / context creation; every accepted value gives identical results
-// (the two result-altering ablations are settable under -DRS_EXPERIMENTS only).  Neither per-context nor thread-safe:
+// (the result-altering ntt_repeat is settable under -DRS_EXPERIMENTS only).  Neither per-context nor thread-safe:
 // tests and tools/ flip knobs between calls, from one thread; the product never changes one.
 //
 // Row: X(name, default, rule, lo, hi, reject, meaning); lo, hi and reject (the message of a rejection, after the name) matter
 // to RANGE only.  Rules (rs::TuneRule) -- ANY: stored as given; BOOL: stored value ? 1 : 0; MIN1: stored max(1, value);
-// RANGE: outside [lo, hi] rejected (RS_ERR_INVALID); FORCE_BC: 0 or 5..20 (tune_check_force_bc, rs_core.hip); SUB_CT: release
-// build 0 or 2, others RS_ERR_UNSUPPORTED, experiments build any (tune_check_sub_ct, rs_core.hip).
+// RANGE: outside [lo, hi] rejected (RS_ERR_INVALID); FORCE_BC: 0 or 5..20 (tune_check_force_bc, rs_core.hip); SUB_CT: 0 or 2,
+// others RS_ERR_UNSUPPORTED (tune_check_sub_ct, rs_core.hip).
 #pragma once
 #include <climits>
 
 #define RS_TUNING_KNOBS(X)                                                                                                        \
-  X(ntt_variant, 14, ANY, 0, 0, "", "negacyclic transform kernel, see launch_ntt (14: wide kernels of ntt_wide.hpp)")                 \
+  X(ntt_variant, 14, ANY, 0, 0, "", "negacyclic transform kernel, see launch_ntt -- 14: wide kernels of ntt_wide.hpp at 2^12..2^14, else as 8; 8..13: wave-private kernel where the length allows, else as 0; others: barrier kernel") \
   X(force_int_arith, 0, BOOL, 0, 0, "", "contexts created from now on use Montgomery integers whatever the prime sizes (tests)")      \
-  X(mac_variant, 5, ANY, 0, 0, "", "6: as 5, one-key launches at N_enc = 8192 in the 512-thread shape (mac_kernel_v4<13, ., 1>); 5: half-spectrum wide kernel at N_enc = 8192 (else as 3); 3: streaming kernel, 1024-thread shape at N_enc = 8192 (else as 2); 2: 512-thread streaming kernel; 1: generic kernel")          \
+  X(mac_variant, 5, ANY, 0, 0, "", ">= 5: wide kernels at N_enc = 8192 and 16384 (mac_kernel_v3 / mac_kernel_v4), else as 4; 2..4: 512-thread streaming kernel at N_enc = 2048..8192 (mac_kernel_v2; 2: generic kernel for two key vectors); <= 1: generic kernel") \
   X(mac_ct_temporal, 0, BOOL, 0, 0, "", "mac_kernel_v3 reads the ciphertext words with temporal loads (A/B of L2 hits on a shared key)") \
   X(plain_variant, 1, ANY, 0, 0, "", "1: plain_center_wide_kernel at N_enc = 8192; 0: plain_center_kernel")                           \
   X(prover_lin_io, 1, ANY, 0, 0, "", "io vectors of groth16::prover as linear forms (MsmLin)")                                        \
@@ -34,7 +34,7 @@
   X(witness_bc2, 1, BOOL, 0, 0, "", "two-dimensional block convolutions where they apply (0: the pairwise form); plans built afterwards") \
   X(witness_inc, 1, BOOL, 0, 0, "", "ring primes without a 2M-th root of unity run INCOMPLETE transforms (witness_inc.hpp) where build_plan's conditions hold; 0: block convolutions; plans built afterwards")                  \
   X(witness_tree_log, 14, RANGE, 13, 14, "must be 13 or 14", "largest tile (log2) of the wide product-tree kernel")                                   \
-  X(witness_sub_ct, 2, SUB_CT, 0, 0, "", "2^13 sub-transforms of the multi-pass path -- 2: sub_ntt_wide_kernel; 0: generic kernel; 1 (sub_ntt_ct_kernel) and 3 (sub_ntt_wide16_kernel): superseded, experiments build only")  \
+  X(witness_sub_ct, 2, SUB_CT, 0, 0, "", "2^13 sub-transforms of the multi-pass path -- 2: sub_ntt_wide_kernel; 0: generic kernel; 1 and 3 (retired kernels): RS_ERR_UNSUPPORTED")  \
   X(witness_tree_ct, 2, ANY, 0, 0, "", "2: wide product-tree kernel (tree_wide_kernel); 1: level-unrolled tree_columns_kernel; 0: level loop") \
   X(witness_tree_fwd, 0, BOOL, 0, 0, "", "the 2^14 tile kernel runs the forward cross stages of level 15 (off: measured slower, see tree_fwd_ok)") \
   X(witness_level_turn, 1, BOOL, 0, 0, "", "fuse the last inverse cross pass of tree level l with the first forward pass of level l + 1") \
@@ -43,10 +43,9 @@
   X(witness_big_ws_mib, 6144, RANGE, 64, INT_MAX, "must be at least 64", "the two [cols][2M] workspaces of a multi-pass sub-chunk of columns")           \
   X(witness_col_budget_mib, 16384, RANGE, 1, INT_MAX, "must be positive", "column workspace of one chunk of the witness map")                         \
   X(witness_lds_logM, 13, RANGE, 6, 13, "must be in [6, 13]", "largest column (log2) that runs entirely inside one LDS tile")
-// These two CHANGE THE RESULTS (timing experiments of tools/): members always, keys of the table under RS_EXPERIMENTS only.
-#define RS_TUNING_KNOBS_EXPERIMENTS(X)                                                       \
-  X(ntt_repeat, 1, ANY, 0, 0, "", "wave-private transform kernel: low 8 bits = runs of the transform on its LDS tile, bits 8.. = stagger_start units")         \
-  X(mac_ablate, 0, ANY, 0, 0, "", "mac_kernel_v2<512, 13, ABLATE>: 1 skips the transform, 2 the ciphertext loads, 4 the C loads")
+// This one CHANGES THE RESULTS (timing experiments of tools/): a member always, a key of the table under RS_EXPERIMENTS only.
+#define RS_TUNING_KNOBS_EXPERIMENTS(X) \
+  X(ntt_repeat, 1, ANY, 0, 0, "", "wave-private transform kernel: low 8 bits = runs of the transform on its LDS tile, bits 8.. = stagger_start units")
 
 namespace rs {
 enum class TuneRule { ANY, BOOL, MIN1, RANGE, FORCE_BC, SUB_CT };

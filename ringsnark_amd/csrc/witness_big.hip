@@ -106,7 +106,6 @@ static void launch_sub_inc(rs_ctx *ctx, typename ArithOf<M>::T *X, size_t ncols,
   const size_t lds = padded_len((size_t)1 << logB) * sizeof(double);
   const size_t bpc = (size_t)1 << (logtot - logB);
   static const char *const names[5] = {"sub_ntt_kernel<0", "sub_ntt_kernel<1", "sub_ntt_kernel<2", "sub_ntt_kernel<3", "sub_ntt_kernel<4"};
-  static const char *const names_ct[5] = {"sub_ntt_ct_kernel<0, 13>", "sub_ntt_ct_kernel<1, 13>", "sub_ntt_ct_kernel<2, 13>", "sub_ntt_ct_kernel<3, 13>", "sub_ntt_ct_kernel<4, 13>"};
   // names as rocprofv3 prints them: "sub_ntt_wide_kernel<MODE, INC>"
   static const char *const names_wide[5][5] = {
       {"sub_ntt_wide_kernel<0, 0>", "sub_ntt_wide_kernel<0, 1>", "sub_ntt_wide_kernel<0, 2>", "sub_ntt_wide_kernel<0, 3>", "sub_ntt_wide_kernel<0, 4>"},
@@ -121,15 +120,10 @@ static void launch_sub_inc(rs_ctx *ctx, typename ArithOf<M>::T *X, size_t ncols,
       {"sub_ntt_w12_kernel<3, 0>", "sub_ntt_w12_kernel<3, 1>", "sub_ntt_w12_kernel<3, 2>", "sub_ntt_w12_kernel<3, 3>", "sub_ntt_w12_kernel<3, 4>"},
       {"sub_ntt_w12_kernel<4, 0>", "", "", "", ""}};
   RS_REQUIRE(inc >= 0 && inc <= RS_INC_MAX && (inc == 0 || (MODE != 1 && MODE != 4)) && logB > inc, "internal: sub-transform launch out of range");
-#ifdef RS_EXPERIMENTS
-  const bool ct = FP && logB == 13 && MODE != 1 && g_tune.witness_sub_ct && (MODE != 4 || g_tune.witness_sub_ct == 2) && (inc == 0 || g_tune.witness_sub_ct == 2);  // MODE 4: generic, wide and 2^12 kernels only
-#else
-  const bool ct = FP && logB == 13 && MODE != 1 && g_tune.witness_sub_ct == 2;  // 0: the generic kernel; 1 and 3 exist in the experiments build only
-#endif
+  const bool ct = FP && logB == 13 && MODE != 1 && g_tune.witness_sub_ct == 2;  // 0: the generic kernel
   const double Bn = (double)((size_t)1 << logB), blocks = (double)(ncols * bpc);
-  static const char *const names_w16[5] = {"sub_ntt_wide16_kernel<0>", "sub_ntt_wide16_kernel<1>", "sub_ntt_wide16_kernel<2>", "sub_ntt_wide16_kernel<3>", "sub_ntt_wide16_kernel<4>"};
   const bool w12 = FP && logB == 12 && MODE != 1 && g_tune.witness_sub_log == 12;
-  ProfScope prof(ctx, st, w12 ? names_w12[MODE][inc] : ct ? (g_tune.witness_sub_ct == 3 ? names_w16[MODE] : g_tune.witness_sub_ct == 2 ? names_wide[MODE][inc] : names_ct[MODE]) : names[MODE], blocks * Bn * (MODE == 4 ? 32.0 : MODE == 3 ? 24.0 : 16.0),
+  ProfScope prof(ctx, st, w12 ? names_w12[MODE][inc] : ct ? names_wide[MODE][inc] : names[MODE], blocks * Bn * (MODE == 4 ? 32.0 : MODE == 3 ? 24.0 : 16.0),
                  blocks * ((MODE >= 2 ? 2.0 : 1.0) * ntt_fp64(Bn, logB - inc) + (MODE == 4 ? 24.0 * Bn : MODE >= 2 ? pointwise_fp64(inc) * Bn : 0.0)));
   static TabPtrs none{};
   const TabPtrs &tp = tabs ? *tabs : none;
@@ -155,16 +149,6 @@ static void launch_sub_inc(rs_ctx *ctx, typename ArithOf<M>::T *X, size_t ncols,
       RS_HIP(hipGetLastError());
       return;
     }
-#ifdef RS_EXPERIMENTS
-    if (logB == 13 && MODE != 1 && MODE != 4 && g_tune.witness_sub_ct == 3 && inc == 0) {
-      const int wl = (int)(WideShape<13>::TILE * sizeof(double));
-      set_max_dyn_lds((const void *)sub_ntt_wide16_kernel<MODE>, wl);
-      hipLaunchKernelGGL((sub_ntt_wide16_kernel<MODE>), dim3((unsigned)std::min<unsigned long long>(nb, 512)), dim3(512), wl, st, X,
-                         logsub - logB, tp, (unsigned)std::max<size_t>(1, tab_period), (unsigned)bpc, col0, (unsigned)S, (unsigned)spl, cp, nb);
-      RS_HIP(hipGetLastError());
-      return;
-    }
-#endif
     if (logB == 13 && MODE != 1 && g_tune.witness_sub_ct == 2) {
       const int wl = (int)(WideShape<13>::TILE * sizeof(double));
 #define RS_WIDE_LAUNCH(INC)                                                                                                             \
@@ -189,15 +173,6 @@ static void launch_sub_inc(rs_ctx *ctx, typename ArithOf<M>::T *X, size_t ncols,
       RS_HIP(hipGetLastError());
       return;
     }
-#ifdef RS_EXPERIMENTS
-    if (logB == 13 && MODE != 1 && MODE != 4 && g_tune.witness_sub_ct && inc == 0) {
-      set_max_dyn_lds((const void *)sub_ntt_ct_kernel<MODE, 13>, (int)lds);
-      hipLaunchKernelGGL((sub_ntt_ct_kernel<MODE, 13>), dim3((unsigned)(ncols * bpc)), dim3(512), lds, st, X, logsub - logB, tp,
-                         (unsigned)std::max<size_t>(1, tab_period), (unsigned)bpc, col0, (unsigned)S, (unsigned)spl, cp);
-      RS_HIP(hipGetLastError());
-      return;
-    }
-#endif
   }
   // the generic kernel reads every column's inc from its plan
   launch_sub_generic<M>(MODE, X, ncols * bpc, logB, logsub - logB, tp, tab_period, bpc, col0, S, spl, cp, lds, st);

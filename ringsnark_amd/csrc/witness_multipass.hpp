@@ -2,9 +2,6 @@
 #pragma once
 #include "witness_cols.hpp"
 #include "witness_inc.hpp"
-#ifdef RS_EXPERIMENTS
-#include "witness_tiles.hpp"  // TreeMulFactory (sub_ntt_ct_kernel)
-#endif
 
 namespace rs {
 
@@ -702,82 +699,13 @@ sub_ntt_kernel(typename CPS::T *__restrict__ X, int logB, int log_n1, TabPtrs ta
   for (int i = threadIdx.x; i < Bn; i += blockDim.x) x[i] = s[pidx(i)];
 }
 
-// Last forward round of a fused sub-transform: spectrum times a table that is itself a lazily reduced
-// spectrum (MODE 3: the other workspace).
-struct SubMulLazyOut {
-  double *sb;
-  const double *dh;
-  Mod mod;
-  __device__ __forceinline__ int pbase(int base) const { return pidx(base); }
-  __device__ __forceinline__ void store(int base, int pb, int eoff, int poff, double v) const {
-    sb[pcomb(pb, poff)] = mulmod(reduce(v, mod), reduce(dh[base + eoff], mod), mod);
-  }
-};
-struct SubMulLazyFactory {
-  double *s;
-  const double *dh_tile;
-  Mod mod;
-  __device__ __forceinline__ SubMulLazyOut operator()(int off) const { return SubMulLazyOut{s + pidx(off), dh_tile + off, mod}; }
-};
-
-#ifndef RS_SUB_MAXR
-#define RS_SUB_MAXR 4  // radix of the wave-private rounds of sub_ntt_ct_kernel
-#endif
-#ifdef RS_EXPERIMENTS  // superseded A/B variant (witness_sub_ct = 1): experiments build only
-// sub_ntt_kernel for the production tile (Bn = 2^LOGB, compile time; 512 threads, two workgroups per CU):
-//   * the cross-wave round of the forward transform reads the block straight from global memory and the
-//     cross-wave round of the inverse writes it straight back (no staging pass, no extra barriers);
-//   * the table product rides the last forward round's store (no separate pointwise pass);
-//   * forward-only blocks (MODE 0) are stored by the wave that finished them.
-// Same arithmetic and operation order per coefficient as sub_ntt_kernel: results are identical.
-template <int MODE, int LOGB>
-__global__ void __launch_bounds__(512, 4)
-sub_ntt_ct_kernel(double *__restrict__ X, int log_n1, TabPtrs tabs, unsigned tab_period, unsigned blocks_per_col, size_t col0,
-                  unsigned S, unsigned slots_per_limb, ColPlans plans) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *s = reinterpret_cast<double *>(smem);
-  constexpr int LOGW = 3, Bn = 1 << LOGB;
-  const size_t blk = blockIdx.x;
-  const size_t col = blk / blocks_per_col;
-  const int limb = (int)(((col0 + col) % S) / slots_per_limb);
-  const ColPlan &P = plans.l[limb];
-  const Mod mod = P.mod;
-  const int root = (1 << log_n1) + (int)(blk & ((1u << log_n1) - 1));
-  const int logn = LOGB + log_n1;
-  double *x = X + blk * (size_t)Bn;
-  const GlobalF64IO gio{x};
-  const ColBlockFactory bf{s};
-  const uint32_t fmask = P.fmask[logn] >> log_n1, imask = P.imask[logn];
-  if (MODE == 0) {
-    lds_ntt_fwd_wp<RS_SUB_MAXR, GlobalF64IO, ColBlockFactory, 3>(s, gio, bf, LOGB, LOGW, P.tw, mod, fmask, root);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    constexpr int BS = Bn >> LOGW;
-    const int off = wave * BS;
-    const double *sb = s + pidx(off);
-    const int p0 = pidx(lane);
-#pragma unroll
-    for (int j = 0; j < BS / 64; j++) x[off + lane + 64 * j] = sb[own_pidx(p0, lane, j)];
-    return;
-  }
-  if (MODE == 2) {
-    const double *tab = static_cast<const double *>(tabs.t[limb]) + (size_t)(blk % tab_period) * Bn;
-    lds_ntt_fwd_wp<RS_SUB_MAXR, GlobalF64IO, TreeMulFactory, 3>(s, gio, TreeMulFactory{s, tab, mod}, LOGB, LOGW, P.tw, mod, fmask, root);
-  } else {
-    const double *tab = static_cast<const double *>(tabs.t[0]) + blk * (size_t)Bn;
-    lds_ntt_fwd_wp<RS_SUB_MAXR, GlobalF64IO, SubMulLazyFactory, 3>(s, gio, SubMulLazyFactory{s, tab, mod}, LOGB, LOGW, P.tw, mod, fmask, root);
-  }
-  lds_ntt_inv_wp<RS_SUB_MAXR, ColBlockFactory, GlobalF64IO, 3>(s, bf, gio, LOGB, LOGW, P.itw, mod, imask, root);
-}
-
-#endif  // RS_EXPERIMENTS
-
-// sub_ntt_ct_kernel in the wide form of ntt_wide.hpp (g_tune.witness_sub_ct == 2): 256 threads x 32 coefficients per block of
+// sub_ntt_kernel at 2^13 in the wide form of ntt_wide.hpp (g_tune.witness_sub_ct == 2): 256 threads x 32 coefficients per block of
 // 2^13, persistent, two workgroups per CU.  Forward rounds (4, 5, 4 stages); round 3 leaves every thread with 16
 // CONSECUTIVE spectrum points per group, which is exactly the operand set of the inverse's first round, so the table
 // product and inverse stages 0..3 follow in registers: the fused forward-multiply-inverse exchanges the tile four
 // times (eight LDS passes) instead of seven.  The twiddles of a block depend on its position in the long transform
 // (root), so they are fetched per block from the L2-resident table.  Same stage arithmetic and reduction points as
-// sub_ntt_ct_kernel: the stored (lazily reduced) values are identical.
+// sub_ntt_kernel: the stored (lazily reduced) values are identical.
 struct SubTw {  // twiddle fetch: 2^k consecutive table entries, 16-byte loads where the run allows
   template <int CNT>
   __device__ static __forceinline__ void run(const double *__restrict__ p, double *dst) {
@@ -1207,176 +1135,6 @@ sub_ntt_w12_kernel(double *__restrict__ X, int log_n1, TabPtrs tabs, unsigned ta
     for (int e = 0; e < 16; e++) __builtin_nontemporal_store(v[e], xb + t + 256 * e);
   }
 }
-
-#ifdef RS_EXPERIMENTS  // superseded A/B variant (witness_sub_ct = 3, measured 11 % slower): experiments build only
-// sub_ntt_wide_kernel at FOUR waves per SIMD (g_tune.witness_sub_ct == 3): 512 threads x 16 coefficients per block of 2^13,
-// <= 128 registers, two workgroups (16 waves) per CU.  Forward rounds of 4, 3 and 2 stages, then the same fused middle
-// as the 32-coefficient form on 16 consecutive points (forward stages 9..12, table product, inverse stages 0..3), then
-// the mirror image: six tile exchanges instead of four, twice the waves to hide them behind.  Same stages, reduction
-// points and products: identical stored values.
-template <int MODE>
-__global__ void __launch_bounds__(512, 4)
-sub_ntt_wide16_kernel(double *__restrict__ X, int log_n1, TabPtrs tabs, unsigned tab_period, unsigned blocks_per_col, size_t col0,
-                      unsigned S_, unsigned slots_per_limb, ColPlans plans, unsigned long long nblocks) {
-  using S = WideShape<13>;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *s = reinterpret_cast<double *>(smem);
-  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-  const int pt = t + (t >> 4);  // px(t), t < 512
-  double pre[16];
-  auto issue_loads = [&](unsigned long long b) {
-    const double *src = X + b * (size_t)S::N + t;
-#pragma unroll
-    for (int e = 0; e < 16; e++) pre[e] = src[512 * e];
-  };
-  unsigned long long blk = blockIdx.x;
-  if (blk < nblocks) issue_loads(blk);
-  for (; blk < nblocks; blk += gridDim.x) {
-    const size_t col = blk / blocks_per_col;
-    const int limb = (int)(((col0 + col) % S_) / slots_per_limb);
-    const ColPlan &P = plans.l[limb];
-    const Mod mod = P.mod;
-    const int root = (1 << log_n1) + (int)(blk & ((1u << log_n1) - 1));
-    const int logn = 13 + log_n1;
-    const uint32_t fmask = P.fmask[logn] >> log_n1, imask = P.imask[logn];
-    const double *__restrict__ tw = P.tw;
-    const double *__restrict__ itw = P.itw;
-    double v[16];
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-      v[e] = pre[e];
-      pin(v[e]);
-    }
-    mem_fence();
-    const unsigned long long bn = blk + gridDim.x;
-    if (bn < nblocks) issue_loads(bn);
-    mem_fence();
-    // ---- forward round 1: stages 0..3 on elements t + 512 e (uniform twiddles)
-    reg_fwd_stages<4, true>(v, mod, fmask, [&](int k, int b) { return tw[(root << k) + b]; });
-    __syncthreads();  // the previous block's last-round reads of the tile are done
-#pragma unroll
-    for (int e = 0; e < 16; e++) s[pt + S::SP * e] = v[e];
-    __syncthreads();
-    // ---- forward round 2: stages 4..6 on hi*512 + lo + 64 e; hi = wave + 8 j is wave-uniform
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      const int hi = __builtin_amdgcn_readfirstlane(wave + 8 * j);
-      const int pb = hi * S::SP + lane + (lane >> 4);
-      double x[8];
-#pragma unroll
-      for (int e = 0; e < 8; e++) x[e] = s[pb + 68 * e];
-      reg_fwd_stages<3, true>(x, mod, fmask >> 4, [&](int k, int b) { return tw[(root << (4 + k)) + (hi << k) + b]; });
-#pragma unroll
-      for (int e = 0; e < 8; e++) s[pb + 68 * e] = x[e];
-    }
-    __syncthreads();
-    // ---- forward round 3: stages 7..8 on hi*64 + lo + 16 e
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int g = t + 512 * j, lo = g & 15, hi = g >> 4;
-      const int pb = hi * 68 + (hi >> 3) * 16 + lo;
-      double x[4];
-#pragma unroll
-      for (int e = 0; e < 4; e++) x[e] = s[pb + 17 * e];
-      const double w0 = tw[(root << 7) + hi];
-      const double2 w12 = reinterpret_cast<const double2 *>(tw + (root << 8) + (hi << 1))[0];
-      reg_fwd_stages<2, true>(x, mod, fmask >> 7, [&](int k, int b) { return k == 0 ? w0 : (b == 0 ? w12.x : w12.y); });
-#pragma unroll
-      for (int e = 0; e < 4; e++) s[pb + 17 * e] = x[e];
-    }
-    __syncthreads();
-    // ---- the middle on the 16 consecutive points of group t: forward stages 9..12, table product, inverse stages 0..3
-    {
-      const int pb = 17 * t + (t >> 5) * 16;  // px(16 t)
-      double w[15];
-      SubTw::run<1>(tw + (root << 9) + t, w);
-      SubTw::run<2>(tw + (root << 10) + (t << 1), w + 1);
-      SubTw::run<4>(tw + (root << 11) + (t << 2), w + 3);
-      SubTw::run<8>(tw + (root << 12) + (t << 3), w + 7);
-      double x[16];
-#pragma unroll
-      for (int e = 0; e < 16; e++) x[e] = s[pb + e];
-      reg_fwd_stages<4, true>(x, mod, fmask >> 9, [&](int k, int b) { return w[(1 << k) - 1 + b]; });
-      if (MODE != 0) {
-        // the wave's 64 groups are 1024 consecutive table words: coalesced loads, handed over through its (free) range
-        const double *tab = (MODE == 2) ? static_cast<const double *>(tabs.t[limb]) + (size_t)(blk % tab_period) * S::N
-                                        : static_cast<const double *>(tabs.t[0]) + blk * (size_t)S::N;
-        const int r0 = wave * 1024;
-        const int p0 = S::px(r0 + 2 * lane);
-        const double2 *t2 = reinterpret_cast<const double2 *>(tab + r0) + lane;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-          const double2 v2 = t2[64 * i];
-          s[p0 + S::px128(i)] = v2.x;
-          s[p0 + S::px128(i) + 1] = v2.y;
-        }
-        wave_sync();
-        if (MODE == 2) {
-#pragma unroll
-          for (int e = 0; e < 16; e++) x[e] = mulmod(reduce(x[e], mod), s[pb + e], mod);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 16; e++) x[e] = mulmod(reduce(x[e], mod), reduce(s[pb + e], mod), mod);
-        }
-        SubTw::run<8>(itw + ((size_t)root << 12) + (t << 3), w);
-        SubTw::run<4>(itw + ((size_t)root << 11) + (t << 2), w + 8);
-        SubTw::run<2>(itw + ((size_t)root << 10) + (t << 1), w + 12);
-        SubTw::run<1>(itw + ((size_t)root << 9) + t, w + 14);
-        reg_inv_stages<4, true>(x, mod, imask, [&](int k, int i) { return w[16 - (16 >> k) + i]; });
-      }
-#pragma unroll
-      for (int e = 0; e < 16; e++) s[pb + e] = x[e];
-    }
-    if (MODE == 0) {  // forward only: every wave streams out the 1024 points its own groups cover
-      wave_sync();
-      const int r0 = wave * 1024;
-      const int p0 = S::px(r0 + 2 * lane);
-      double2 *d2 = reinterpret_cast<double2 *>(X + blk * (size_t)S::N + r0) + lane;
-#pragma unroll
-      for (int i = 0; i < 8; i++) d2[64 * i] = make_double2(s[p0 + S::px128(i)], s[p0 + S::px128(i) + 1]);
-      continue;
-    }
-    __syncthreads();
-    // ---- inverse round 3: stages 4..5 on hi*64 + lo + 16 e; block of stage 4+k: (hi << (1-k)) + (e >> (k+1)) of 256 >> k
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int g = t + 512 * j, lo = g & 15, hi = g >> 4;
-      const int pb = hi * 68 + (hi >> 3) * 16 + lo;
-      double x[4];
-#pragma unroll
-      for (int e = 0; e < 4; e++) x[e] = s[pb + 17 * e];
-      const double2 w01 = reinterpret_cast<const double2 *>(itw + ((size_t)root << 8) + (hi << 1))[0];
-      const double w2 = itw[((size_t)root << 7) + hi];
-      reg_inv_stages<2, true>(x, mod, imask >> 4, [&](int k, int i) { return k == 0 ? (i == 0 ? w01.x : w01.y) : w2; });
-#pragma unroll
-      for (int e = 0; e < 4; e++) s[pb + 17 * e] = x[e];
-    }
-    __syncthreads();
-    // ---- inverse round 2: stages 6..8 on hi*512 + lo + 64 e; block of stage 6+k: (hi << (2-k)) + (e >> (k+1)) of 64 >> k
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      const int hi = __builtin_amdgcn_readfirstlane(wave + 8 * j);
-      const int pb = hi * S::SP + lane + (lane >> 4);
-      double x[8];
-#pragma unroll
-      for (int e = 0; e < 8; e++) x[e] = s[pb + 68 * e];
-      reg_inv_stages<3, true>(x, mod, imask >> 6, [&](int k, int i) { return itw[((size_t)root << (6 - k)) + (hi << (2 - k)) + i]; });
-#pragma unroll
-      for (int e = 0; e < 8; e++) s[pb + 68 * e] = x[e];
-    }
-    __syncthreads();
-    // ---- inverse round 1: stages 9..12 on elements t + 512 e; block of stage 9+k: e >> (k+1) of 8 >> k
-#pragma unroll
-    for (int e = 0; e < 16; e++) v[e] = s[pt + S::SP * e];
-    reg_inv_stages<4, true>(v, mod, imask >> 9, [&](int k, int i) { return itw[((8 >> k) * root) + i]; });
-    {
-      double *dst = X + blk * (size_t)S::N + t;
-#pragma unroll
-      for (int e = 0; e < 16; e++) dst[512 * e] = v[e];
-    }
-  }
-}
-#endif  // RS_EXPERIMENTS
 
 // ZK patch of the multi-pass H: H += d2*A + d1*B + d1*d2*Z, H[0] -= d3; then canonical form.
 template <class CPS>

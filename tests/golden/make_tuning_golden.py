@@ -31,7 +31,7 @@ KNOBS = [
     ("witness_tree_once", 1, "bool"), ("witness_big_ws_mib", 6144, "checked"), ("witness_col_budget_mib", 16384, "checked"),
     ("witness_lds_logM", 13, "checked"),
 ]
-EXPERIMENTS = [("ntt_repeat", 1, "any"), ("mac_ablate", 0, "any")]  # keys of the experiments build only: unknown to the release library
+EXPERIMENTS = [("ntt_repeat", 1, "any")]  # key of the experiments build only: unknown to the release library
 UNKNOWN = "no_such_knob"
 
 

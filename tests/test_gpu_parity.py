@@ -53,6 +53,42 @@ def test_ntt_matches_oracle(name):
             assert (host(d) == a).all()
 
 
+def test_ntt_variants_select_three_kernels_with_equal_results():
+    """ntt_variant 0 / 8..13 / 14 = barrier / wave-private / wide kernel.  2^5 points run the barrier kernel whatever the
+    knob, 2^11 the wave-private one from 8 on, 2^13 the wide ones at 14: every value gives the same bits and the round trip
+    returns the input; at 2^13 the profile shows one kernel for 8 and 12 and another for 14."""
+    import torch
+    from ringsnark_amd.device import Device
+    for logn, prm in ((5, P.make_params(16, [30], 32, [40], ring_factor=1 << 12)), (11, P.make_params(1024, [30], 2048, [43])),
+                      (13, P.preset("C2"))):
+        assert prm.N_enc == 1 << logn
+        dev = dev_for("C2") if logn == 13 else Device(prm)
+        src = torch.empty((3, prm.N_enc), dtype=torch.int64, device=dev.device).random_(0, int(prm.Q[0]))
+        fwd, kernels = {}, {}
+        dev.set_profiling(True)
+        try:
+            for v in (0, 8, 12, 14):
+                with _lib.tuning(ntt_variant=v):
+                    d = src.clone()
+                    dev.profile_read()
+                    dev.ntt(d, _lib.RS_MOD_COEFF, 0)
+                    kernels[v] = [(k["name"], k["launches"]) for k in dev.profile_read()]
+                    fwd[v] = d.clone()
+                    dev.ntt(d, _lib.RS_MOD_COEFF, 0, inverse=True)
+                    assert (d == src).all(), ("roundtrip", logn, v)
+        finally:
+            dev.set_profiling(False)
+        for v in fwd:
+            assert (fwd[v] == fwd[0]).all(), (logn, v)
+            assert len(kernels[v]) == 1 and kernels[v][0][1] == 1, (logn, v, kernels[v])  # one launch of one kernel
+        if logn == 5:
+            assert kernels[0] == kernels[8] == kernels[12] == kernels[14], kernels
+        elif logn == 11:
+            assert kernels[8] == kernels[12] == kernels[14] and kernels[0] != kernels[8], kernels
+        else:
+            assert kernels[8] == kernels[12] and kernels[14] != kernels[8] and kernels[0] != kernels[8], kernels
+
+
 @pytest.mark.parametrize("name", ["toy", "toy49", "C2", "toy54", "toy60", "micro60", "toy+int"])
 def test_ring_ops_match_oracle(name):
     dev = dev_for(name)
@@ -249,9 +285,10 @@ def test_grouped_msm_with_vectors_of_different_lengths(name):
 @pytest.mark.parametrize("name", ["C2", "C3"])
 def test_wide_kernels_equal_their_predecessors_and_the_oracle(name):
     """N_enc = 8192: the wide NTT (ntt_variant 14), the half-spectrum MAC (mac_variant 5) and the wide plaintext kernel
-    with paired rows (plain_variant 1) against the kernels they replaced, on a grouped inner product with a zero term, a
-    one-limb-zero term, a Scalar-1 term and a short vector; one configuration also against the oracle.  C2 has
-    N = 4096 < N_enc (slots beyond N stay zero), C3 N = N_enc."""
+    with paired rows (plain_variant 1) against their fallbacks -- the barrier and wave-private NTT kernels (ntt_variant 0
+    and 12), mac_kernel_v2<512> (mac_variant 3; 6 is a synonym of 5) and plain_center_kernel -- on a grouped inner product
+    with a zero term, a one-limb-zero term, a Scalar-1 term and a short vector; one configuration also against the oracle.
+    C2 has N = 4096 < N_enc (slots beyond N stay zero), C3 N = N_enc."""
     import torch
     dev = dev_for(name)
     prm = dev.prm
@@ -260,7 +297,7 @@ def test_wide_kernels_equal_their_predecessors_and_the_oracle(name):
     for modset, idx, q in ((_lib.RS_MOD_COEFF, prm.K - 1, prm.Q[-1]), (_lib.RS_MOD_PLAIN, 0, prm.q[0])):
         src = torch.empty((37, prm.N_enc), dtype=torch.int64, device=dev.device).random_(0, int(q))
         outs = []
-        for v in (0, 12, 14):
+        for v in (0, 12, 14):  # barrier kernel, wave-private kernel, wide kernels
             with _lib.tuning(ntt_variant=v):
                 d = src.clone()
                 dev.ntt(d, modset, idx)
@@ -279,7 +316,7 @@ def test_wide_kernels_equal_their_predecessors_and_the_oracle(name):
     kinds[4] = O.KIND_ONE
     vecs = [(dev.put(v[0]), kinds, 0), (dev.put(v[1]), None, 0), (dev.put(v[2]), None, 1)]
     res = {}
-    for mv, pv in ((5, 1), (3, 0), (5, 0), (3, 1), (6, 1), (6, 0)):  # 6: one key vector in the 512-thread shape (mac_kernel_v4<13, ., 1>)
+    for mv, pv in ((5, 1), (3, 0), (5, 0), (3, 1), (6, 1), (6, 0)):  # 3: mac_kernel_v2<512>; 5 and 6: mac_kernel_v3
         with _lib.tuning(mac_variant=mv, plain_variant=pv):
             out, used = dev.msm([dev.put(encs)], vecs, 2, want_used=True)
             res[(mv, pv)] = (host(out), used)
@@ -951,8 +988,8 @@ def test_host_resident_key_equals_the_device_resident_one(name, tile):
 @pytest.mark.parametrize("m,zk", [(20000, True), (40000, False)])
 def test_multipass_tuned_sub_transform_kernel_equals_generic(m, zk):
     """M >= 2^15: the multi-pass path runs its 2^13-point sub-transforms through sub_ntt_wide_kernel (32 coefficients
-    per thread, forward - table product - inverse fused through registers) or sub_ntt_ct_kernel (wave-private rounds);
-    both must reproduce the generic kernel bit for bit."""
+    per thread, forward - table product - inverse fused through registers), which must reproduce the generic kernel bit
+    for bit."""
     dev = dev_for("toy44")
     prm = dev.prm
     ctx = H.oracle_ctx(prm)
@@ -964,11 +1001,11 @@ def test_multipass_tuned_sub_transform_kernel_equals_generic(m, zk):
     dcs = dev.r1cs(cs)
     keys = ("A_io", "B_io", "C_io", "A_mid", "B_mid", "C_mid", "H")
     runs = {}
-    for variant in (0, 1, 2, 3):  # generic, wave-private tuned (sub_ntt_ct_kernel), wide (sub_ntt_wide_kernel), wide16
+    for variant in (0, 1, 2, 3):  # generic, retired, wide (sub_ntt_wide_kernel), retired
         with contextlib.ExitStack() as knob:
             try:
                 knob.enter_context(_lib.tuning(witness_sub_ct=variant))
-            except _lib.RsError as e:  # 1 and 3 are superseded A/B variants: experiments build only
+            except _lib.RsError as e:  # 1 and 3 selected superseded A/B kernels
                 assert variant in (1, 3) and e.code == _lib.RS_ERR_UNSUPPORTED
                 continue
             runs[variant] = {k: host(v) for k, v in dev.witness_map(dcs, asg, *ds).items() if k in keys}

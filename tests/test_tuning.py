@@ -2,8 +2,8 @@
 override ringsnark_amd._lib.tuning.  No device is touched: the knobs are host variables of the library.
 
 tests/golden/tuning_table.json (tests/golden/make_tuning_golden.py) is what the release library answered before the table
-existed: the status of every (key, probe value), each key's default and the value an accepted set stores; the two
-experiments-only keys are unknown to it.  Every test leaves every knob at its default (one process with the other tests)."""
+existed: the status of every (key, probe value), each key's default and the value an accepted set stores; the
+experiments-only key is unknown to it.  Every test leaves every knob at its default (one process with the other tests)."""
 import ctypes as C
 import json
 import os

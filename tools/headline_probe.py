@@ -16,7 +16,7 @@ prm = P.preset(sys.argv[4] if len(sys.argv) > 4 else "C3")
 dev = Device(prm)
 import os  # noqa: E402
 from ringsnark_amd import _lib  # noqa: E402
-_lib.tuning_from_env()  # e.g. RS_TUNING=witness_sub_ct=2,ntt_variant=12
+_lib.tuning_from_env()  # e.g. RS_TUNING=witness_sub_ct=0,ntt_variant=8
 m, W = 1 << logm, 1 << logw
 t0 = time.time()
 cs = R.chain_r1cs(m, prm.q)

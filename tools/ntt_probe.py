@@ -1,9 +1,9 @@
-"""Standalone NTT kernel shapes on one GPU (tuning knob "ntt_variant"): one tool for what used to be four scripts.
+"""Standalone NTT kernels on one GPU (tuning knob "ntt_variant": 0 barrier kernel, 8 wave-private kernel, 14 wide kernels).
 
   ntt_probe.py variants [preset] [v,v,...]   every variant: forward equals variant 0, round trip, forward / inverse GB/s
   ntt_probe.py one <variant> [inv] [preset]  three launches of one variant (the command to put under rocprofv3)
-  ntt_probe.py repeat [v,v,...]              compute-only cost: 1 / 5 / 9 in-LDS repetitions ("ntt_repeat"; experiments build)
-  ntt_probe.py stagger [v,v,...]             the same knob's stagger field (bits 8+): workgroups start 0..16 transforms apart
+  ntt_probe.py repeat                        wave-private kernel, compute-only cost: 1 / 5 / 9 in-LDS repetitions ("ntt_repeat"; experiments build)
+  ntt_probe.py stagger                       the same knob's stagger field (bits 8+): workgroups start 0..16 transforms apart
 (bandwidth sweeps over batch sizes: tools/ntt_bw.py)"""
 import os
 import sys
@@ -47,7 +47,7 @@ elif mode == "variants":
     src = torch.empty((B, prm.N_enc), dtype=torch.int64, device=dev.device).random_(0, prm.Q[0])
     ref_f = None
     gb = B * prm.N_enc * 16 / 1e9
-    for v in (ints(sys.argv[3]) if len(sys.argv) > 3 else range(15)):
+    for v in (ints(sys.argv[3]) if len(sys.argv) > 3 else (0, 8, 14)):
         try:
             tune("ntt_variant", v)
         except _lib.RsError as e:
@@ -68,7 +68,7 @@ elif mode in ("repeat", "stagger"):
     prm = P.preset("C3")
     dev = Device(prm)
     d = torch.empty((B, prm.N_enc), dtype=torch.int64, device=dev.device).random_(0, prm.Q[0])
-    for v in (ints(sys.argv[2]) if len(sys.argv) > 2 else (8, 9, 13)):
+    for v in (8,):  # the kernel that reads ntt_repeat
         tune("ntt_variant", v)
         if mode == "repeat":
             res = []
