@@ -1,4 +1,6 @@
 """Shared builders for the parity tests (CPU oracle side)."""
+from fractions import Fraction
+
 import numpy as np
 
 from oracle import oracle as O
@@ -59,3 +61,235 @@ def dft_circuit(prm, ctx, seed=5):
     xs = [ctx.ring_scalar(int(v)) for v in rng.randint(0, 2**16, N)]
     xs.append(lincomb_oracle(ctx, cs)("a", 0, xs))
     return cs, np.ascontiguousarray(np.stack(xs))
+
+
+# ---- sign-aligned worst-case inputs for the inner-product kernels (tests/test_aligned_inputs.py, tests/test_msm_worst_case.py)
+_NTT = {}
+
+
+def _ntt(logn, Q):
+    if (logn, Q) not in _NTT:
+        _NTT[(logn, Q)] = O.NTT(logn, Q)
+    return _NTT[(logn, Q)]
+
+
+def centred_lift(plain, q):
+    """Canonical residues mod q (uint64) -> their balanced representatives (int64): c >= (q + 1) / 2 => c - q."""
+    lift = np.asarray(plain, dtype=np.uint64).astype(np.int64)
+    lift[lift >= (q + 1) // 2] -= q
+    return lift
+
+
+def plain_spectrum(ctx, j, lift):
+    """NTT_{Q_j}(lift mod Q_j) of a row of signed integers [N_enc]: the factor u the kernels multiply a key word by."""
+    Q = ctx.Q[j]
+    return _ntt(ctx.N_enc.bit_length() - 1, Q).fwd((np.asarray(lift, dtype=np.int64) % np.int64(Q)).astype(np.uint64))
+
+
+def term_spectra(ctx, rings, kinds=None, slot_const=False):
+    """u [D][L][K][N_enc] (uint64) of the terms of one coefficient vector.  rings: [D][L][N]; slot_const: [D][L] values (the
+    ring element holds the value in each of its N slots: with N == N_enc its plaintext is the constant polynomial);
+    kinds[d] == KIND_ONE: the plaintext is the constant polynomial 1, the spectrum all ones."""
+    D = len(rings)
+    U = np.empty((D, ctx.L, ctx.K, ctx.N_enc), dtype=np.uint64)
+    for d in range(D):
+        for i in range(ctx.L):
+            if kinds is not None and kinds[d] == O.KIND_ONE:
+                lift = None
+            elif slot_const:  # N == N_enc: the constant polynomial, whose spectrum is the lifted constant everywhere
+                lift = centred_lift(ctx.batch_encode(i, np.full(ctx.N, rings[d][i], dtype=np.uint64)), ctx.q[i])
+            else:
+                lift = centred_lift(ctx.batch_encode(i, rings[d][i]), ctx.q[i])
+            for j in range(ctx.K):
+                if lift is None:
+                    U[d, i, j] = 1
+                else:
+                    U[d, i, j] = plain_spectrum(ctx, j, lift)
+    return U
+
+
+def aligned_sign(i, c, j):
+    """Sign of every target of slab (limb i, component c, prime j): both signs occur in every call (c takes both values)."""
+    return 1 if (i + c + j) % 2 == 0 else -1
+
+
+def aligned_key(ctx, U, seed, frac=0.30):
+    """Key words that turn the spectra U [D][L][K][N_enc] (no zero entry) into chosen products: returns (encs
+    [D][L][2][K][N_enc] uint64, targets, Python integers in the same shape) with
+        target = s (floor(frac Q_j) - r[pos]),  r uniform in [0, 2^20),  s = aligned_sign(i, c, j),
+        ct     = target u^-1 mod Q_j,
+    so that ct u = target (mod Q_j) at every position and all targets of a slab carry one sign."""
+    D = U.shape[0]
+    rng = np.random.RandomState(seed)
+    encs = np.empty(ctx.enc_shape(D), dtype=np.uint64)
+    targets = np.empty(ctx.enc_shape(D), dtype=object)
+    for j, Q in enumerate(ctx.Q):
+        base = int(Fraction(frac) * Q)  # floor(frac Q_j), exactly
+        for d in range(D):
+            for i in range(ctx.L):
+                uinv = np.array([pow(int(x), -1, Q) for x in U[d, i, j]], dtype=object)
+                for c in range(2):
+                    r = rng.randint(0, 1 << 20, size=ctx.N_enc).astype(np.int64)
+                    tgt = (aligned_sign(i, c, j) * (base - r)).astype(object)
+                    targets[d, i, c, j] = tgt
+                    encs[d, i, c, j] = (tgt * uinv % Q).astype(np.uint64)
+    return encs, targets
+
+
+def aligned_terms(ctx, D, seed, frac=0.30, kinds=None, slot_const=False, rings=None):
+    """D terms of an inner product whose every product is a chosen balanced integer of one sign per slab, so that the
+    sum over T terms is as large as T terms can make it.  Returns (rings [D][L][N], encs [D][L][2][K][N_enc], targets); see
+    aligned_key for encs and targets.  The plaintext rows are free (random ring elements from `seed`, redrawn while a
+    spectrum has a zero; or `rings`, an array or -- the vectors of one group, whose lifts the kernels add -- a list of
+    arrays); u = NTT_{Q_j}(centred_lift(batch_encode(i, rings[d, i])) mod Q_j) comes from the CPU oracle.  kinds and
+    slot_const as in term_spectra (slot_const: rings is [D][L]).
+
+    Why frac = 0.30: f64mod.hpp bounds the quotient error of mulmod(a, b) by 3 * 2^-53 * |a b / p|.  Here a is a canonical
+    key word (< p) and b the kernel's representative of u with |b| <= 2^49, so |a b / p| <= 2^49 and the error is at most
+    3 * 2^-4 = 0.1875.  a b / p = integer + target / p with |target / p| <= 0.30, and 0.30 + 0.1875 < 0.5: the rounded
+    quotient is that integer and the kernel's product is exactly `target`, whichever lazy representative of u it holds.
+    The expected sum therefore needs no oracle (closed_form), and an accumulator that is never reduced holds exactly the
+    running sum of the targets."""
+    if rings is None:
+        if slot_const:
+            rng = np.random.RandomState(seed + 1)
+            rings = np.stack([rng.randint(1, 2**62, size=D, dtype=np.int64).astype(np.uint64) % np.uint64(q) for q in ctx.q], axis=1)
+            rings[rings == 0] = 1
+        else:
+            rings = ctx.random_ring(seed + 1, D)
+            if kinds is not None:
+                for d in range(D):
+                    if kinds[d] == O.KIND_ONE:
+                        rings[d] = ctx.ring_scalar(1)
+        U, redraw = term_spectra(ctx, rings, kinds, slot_const), 0
+        while not U.all():
+            for d in sorted(set(np.argwhere(U == 0)[:, 0])):
+                redraw += 1
+                rings[d] = rings[d] + np.uint64(1) if slot_const else ctx.random_ring(seed + 1 + 7919 * redraw)
+                U[d] = term_spectra(ctx, rings[d:d + 1], slot_const=slot_const)[0]
+    else:
+        group = rings if isinstance(rings, (list, tuple)) else [rings]
+        U = np.zeros((D, ctx.L, ctx.K, ctx.N_enc), dtype=np.uint64)
+        for vec in group:
+            Uv = term_spectra(ctx, vec, kinds, slot_const)
+            for j, Q in enumerate(ctx.Q):
+                U[:, :, j] = (U[:, :, j] + Uv[:, :, j]) % np.uint64(Q)  # the transform is linear; both summands < 2^60
+        assert U.all(), "a spectrum of the given rows has a zero: no key word can produce the target there"
+    encs, targets = aligned_key(ctx, U, seed, frac)
+    return rings, encs, targets
+
+
+def aligned_T(Q, frac=0.30, margin=4):
+    """Number of same-sign terms after which an accumulator that is never reduced has left the exactly representable
+    integers: ceil(2^53 / (frac min(Q) - 2^20)) + margin."""
+    assert margin >= 4
+    per_term = Fraction(frac) * min(int(x) for x in Q) - (1 << 20)
+    return -((-(1 << 53) * per_term.denominator) // per_term.numerator) + margin
+
+
+def closed_form(ctx, targets, T):
+    """sum_t targets[t % D] mod Q_j in Python integers: the inner product of T aligned terms, [L][2][K][N_enc] uint64."""
+    D = targets.shape[0]
+    counts = np.bincount(np.arange(T) % D, minlength=D)
+    out = np.empty(ctx.enc_shape(), dtype=np.uint64)
+    for j, Q in enumerate(ctx.Q):
+        s = sum(int(counts[d]) * targets[d, :, :, j] for d in range(D))
+        out[:, :, j] = (s % Q).astype(np.uint64)
+    return out
+
+
+def check_aligned_inputs(ctx, targets, T, frac=0.30):
+    """The conditions on aligned inputs that give a kernel test its meaning, per (limb, component, prime) slab: every
+    |target| <= frac Q_j, one sign, and the running sum over T cyclic terms -- what an accumulator without periodic
+    reduction would hold -- beyond 2^53 in absolute value at some position.  Returns the smallest of the slabs' largest
+    |running sum| / 2^53."""
+    D, reached = targets.shape[0], []
+    for i in range(ctx.L):
+        for c in range(2):
+            for j, Q in enumerate(ctx.Q):
+                slab = np.stack([targets[d, i, c, j].astype(np.int64) for d in range(D)])
+                assert all(abs(int(v)) <= Fraction(frac) * Q for v in (slab.min(), slab.max())), (i, c, j)
+                assert (np.sign(slab) == aligned_sign(i, c, j)).all(), (i, c, j)
+                assert T * int(np.abs(slab).max()) < 2**62  # the int64 running sum below is exact
+                run, peak = np.zeros(slab.shape[1], dtype=np.int64), 0
+                for t in range(T):
+                    run += slab[t % D]
+                    peak = max(peak, int(np.abs(run).max()))
+                assert peak > 2**53, (i, c, j, peak / 2.0**53)
+                reached.append(peak / 2.0**53)
+    return min(reached)
+
+
+EXTREME_PATTERNS = ("plus", "minus", "alternating", "random")
+
+
+def extreme_rows(ctx, limb, pattern, seed=0):
+    """The ring-element row [N] (N == N_enc) whose plaintext has every coefficient at the ends of the balanced range:
+    (q - 1) / 2 (lift +(q - 1) / 2) or (q + 1) / 2 (lift -(q - 1) / 2).  pattern: one of EXTREME_PATTERNS."""
+    assert ctx.N == ctx.N_enc, "every plaintext is a batch encoding only when N == N_enc"
+    q, n = ctx.q[limb], ctx.N_enc
+    if pattern == "plus":
+        minus = np.zeros(n, dtype=bool)
+    elif pattern == "minus":
+        minus = np.ones(n, dtype=bool)
+    elif pattern == "alternating":
+        minus = np.arange(n) % 2 == 1
+    else:
+        assert pattern == "random", pattern
+        minus = np.random.RandomState(seed).randint(0, 2, size=n).astype(bool)
+    poly = np.where(minus, np.uint64((q + 1) // 2), np.uint64((q - 1) // 2)).astype(np.uint64)
+    return ctx.batch_decode(limb, poly)
+
+
+# The contexts of tests/test_msm_worst_case.py, smallest at which each kernel exists: name -> make_params arguments (None: preset)
+WORST_CASES = {
+    "toy49": None,
+    "n2048": (2048, [43], 2048, [49, 48]),
+    "n8192": (8192, [43], 8192, [49, 48]),
+    "n16384": (2048, [43], 16384, [49, 48]),
+    "n8192q44": (8192, [43], 8192, [44]),
+    "hybrid8192": (8192, [54], 8192, [49, 48]),
+    "n16384full": (16384, [43], 16384, [49, 48]),  # N == N_enc at 16384 points: extreme plaintext rows
+}
+ALIGNED_D = 8
+
+
+def worst_case_params(name):
+    args = WORST_CASES[name]
+    return P.preset(name) if args is None else P.make_params(*args, name=name)
+
+
+_ALIGNED = {}
+
+
+def aligned_case(name, variant="poly", key=0):
+    """(ctx, rings, encs, targets, T, kinds) of a worst-case context, built once per process.  variant: "poly" (random ring
+    elements), "one" (every term KIND_ONE), "const" (slot-constant vector: rings is [D][L]); key = 1: a second key, other
+    targets, for the same rows."""
+    if (name, variant, key) not in _ALIGNED:
+        prm = worst_case_params(name)
+        ctx = oracle_ctx(prm)
+        T = aligned_T(prm.Q)
+        seed = 1000 + 16 * sorted(WORST_CASES).index(name) + ("poly", "one", "const").index(variant)
+        kinds = np.full(ALIGNED_D, O.KIND_ONE, dtype=np.uint8) if variant == "one" else None
+        rings = aligned_case(name, variant)[1] if key else None
+        rings, encs, targets = aligned_terms(ctx, ALIGNED_D, seed + 8 * key, kinds=kinds, slot_const=variant == "const", rings=rings)
+        _ALIGNED[(name, variant, key)] = (ctx, rings, encs, targets, T, kinds)
+    return _ALIGNED[(name, variant, key)]
+
+
+EXTREME_CASES = {"n8192": 4, "hybrid8192": 1, "n16384full": 4}  # context -> vectors per group (MAX_GROUP_VECS; hybrid: one)
+
+
+def extreme_case(name):
+    """(ctx, rings [D][L][N], n_vecs, encs, targets, T): D terms whose rows come from extreme_rows, the four patterns in turn
+    (the random one with a new seed each time), and the key aligned to the row a group of n_vecs copies of them sums to
+    (every coefficient +-n_vecs (q - 1) / 2)."""
+    if (name, "extreme") not in _ALIGNED:
+        prm = worst_case_params(name)
+        ctx = oracle_ctx(prm)
+        n_vecs = EXTREME_CASES[name]
+        rings = np.stack([np.stack([extreme_rows(ctx, i, EXTREME_PATTERNS[d % 4], seed=d) for i in range(ctx.L)]) for d in range(ALIGNED_D)])
+        _, encs, targets = aligned_terms(ctx, ALIGNED_D, 2000 + sorted(WORST_CASES).index(name), rings=[rings] * n_vecs)
+        _ALIGNED[(name, "extreme")] = (ctx, rings, n_vecs, encs, targets, aligned_T(prm.Q))
+    return _ALIGNED[(name, "extreme")]

@@ -53,6 +53,50 @@ def test_ntt_matches_oracle(name):
             assert (host(d) == a).all()
 
 
+_NTT_STRUCTURED = {}
+
+
+def _structured_ntt_cases(name):
+    """[(modset, index, inputs [7][n], forward [7][n], inverse [7][n])] per prime of the preset, oracle side, built once."""
+    if name not in _NTT_STRUCTURED:
+        prm = P.preset(name)
+        n, logn = prm.N_enc, prm.N_enc.bit_length() - 1
+        sets = ((_lib.RS_MOD_PLAIN, prm.q), (_lib.RS_MOD_COEFF, prm.Q)) if name != "C5s" else ((_lib.RS_MOD_COEFF, prm.Q),)
+        out = []
+        for modset, primes in sets:
+            for idx, p in enumerate(primes):
+                a = np.zeros((7, n), dtype=np.uint64)
+                a[0] = p - 1
+                a[1] = (p - 1) // 2
+                a[2, 1::2] = p - 1
+                for row, pos in zip(range(3, 7), (0, 1, n // 2, n - 1)):  # unit impulses: the output is a row of twiddles
+                    a[row, pos] = 1
+                t = O.NTT(logn, p)
+                out.append((modset, idx, a, np.stack([t.fwd(x) for x in a]), np.stack([t.inv(x) for x in a])))
+        _NTT_STRUCTURED[name] = out
+    return _NTT_STRUCTURED[name]
+
+
+@pytest.mark.parametrize("batch", [1, 3])
+@pytest.mark.parametrize("variant", [0, 12, 14])
+@pytest.mark.parametrize("inverse", [False, True])
+@pytest.mark.parametrize("name", ["toy49", "C2", "C5s"])
+def test_ntt_structured_inputs_match_oracle(name, inverse, variant, batch):
+    """The standalone transforms on inputs where an error cannot average out: all p - 1, all (p - 1) / 2, alternating
+    0, p - 1, and a unit impulse at 0, 1, n / 2 and n - 1 -- its transform is a row of twiddles, so a wrong table index is a
+    wrong value.  128, 8192 and 16384 points (C5s: the data primes), both directions, the barrier, wave-private and wide
+    kernels (ntt_variant 0, 12, 14), one polynomial per launch and three."""
+    dev = dev_for(name)
+    with _lib.tuning(ntt_variant=variant):
+        for modset, idx, a, fwd, inv in _structured_ntt_cases(name):
+            exp = inv if inverse else fwd
+            for r0 in range(0, 7, batch):
+                rows = [(r0 + k) % 7 for k in range(batch)]
+                d = dev.put(np.ascontiguousarray(a[rows]))
+                dev.ntt(d, modset, idx, inverse=inverse)
+                assert (host(d) == exp[rows]).all(), (name, modset, idx, rows)
+
+
 def test_ntt_variants_select_three_kernels_with_equal_results():
     """ntt_variant 0 / 8..13 / 14 = barrier / wave-private / wide kernel.  2^5 points run the barrier kernel whatever the
     knob, 2^11 the wave-private one from 8 on, 2^13 the wide ones at 14: every value gives the same bits and the round trip
