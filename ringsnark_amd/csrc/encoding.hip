@@ -336,43 +336,7 @@ encode_kernel_int(const uint64_t *__restrict__ rings, const uint64_t *__restrict
   }
 }
 
-struct TabCopiesI {
-  NttTableI *d_plain = nullptr, *d_coeff = nullptr;
-  explicit TabCopiesI(rs_ctx *ctx) {
-    RS_HIP(hipMalloc(&d_plain, sizeof(NttTableI) * ctx->L));
-    RS_HIP(hipMemcpy(d_plain, ctx->plain_i, sizeof(NttTableI) * ctx->L, hipMemcpyHostToDevice));
-    RS_HIP(hipMalloc(&d_coeff, sizeof(NttTableI) * ctx->K));
-    RS_HIP(hipMemcpy(d_coeff, ctx->coeff_i, sizeof(NttTableI) * ctx->K, hipMemcpyHostToDevice));
-  }
-  ~TabCopiesI() {
-    (void)hipFree(d_plain);
-    (void)hipFree(d_coeff);
-  }
-};
-
 static int enc_threads(int logn) { return (int)std::max(64, std::min(1024, (1 << logn) / 8)); }
-
-// small device copies of the tables (allocated per call: generator / verifier paths are not hot)
-struct TabCopies {
-  NttTable *d_plain = nullptr, *d_coeff = nullptr;
-  uint64_t *d_q = nullptr, *d_Q = nullptr;
-  explicit TabCopies(rs_ctx *ctx) {
-    RS_HIP(hipMalloc(&d_plain, sizeof(NttTable) * ctx->L));
-    RS_HIP(hipMemcpy(d_plain, ctx->plain, sizeof(NttTable) * ctx->L, hipMemcpyHostToDevice));
-    RS_HIP(hipMalloc(&d_coeff, sizeof(NttTable) * ctx->K));
-    RS_HIP(hipMemcpy(d_coeff, ctx->coeff, sizeof(NttTable) * ctx->K, hipMemcpyHostToDevice));
-    RS_HIP(hipMalloc(&d_q, sizeof(uint64_t) * ctx->L));
-    RS_HIP(hipMemcpy(d_q, ctx->q, sizeof(uint64_t) * ctx->L, hipMemcpyHostToDevice));
-    RS_HIP(hipMalloc(&d_Q, sizeof(uint64_t) * ctx->K));
-    RS_HIP(hipMemcpy(d_Q, ctx->Q, sizeof(uint64_t) * ctx->K, hipMemcpyHostToDevice));
-  }
-  ~TabCopies() {
-    (void)hipFree(d_plain);
-    (void)hipFree(d_coeff);
-    (void)hipFree(d_q);
-    (void)hipFree(d_Q);
-  }
-};
 
 // Host side of the noise guard: bit_count(Q) and the mixed-radix digits (radices Q_0, Q_1, ...) of 2^b - 1 for every
 // b < bit_count(Q), by exact multi-word arithmetic (K <= 12 words of 62 bits).
@@ -470,8 +434,9 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
                        rs_stream stream) {
   if (count == 0) return RS_OK;
   WsScope ws_scope(ctx, S(stream));  // holds ctx->mu: the lazily built constants below are built once
-  // constants of the context, built at the first call and kept on the device (round-5 advice: no hipMalloc / hipFree, no
-  // pageable upload -- an implicit device-wide synchronisation each -- per verifier decode): the digits of 2^b - 1
+  // Constants of the context that only decoding reads are built at the first call and kept on the device: the digits of
+  // 2^b - 1 here, the per-limb CRT constants below.  With the table arrays of the context itself, a warm decode makes no
+  // hipMalloc / hipFree and no pageable upload (each an implicit device-wide synchronisation; round-5 advice).
   if (!ctx->d_noise_thr) {
     std::vector<uint64_t> thr_h;
     ctx->noise_tb = noise_thresholds(ctx, thr_h);
@@ -490,7 +455,7 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
   }
   const int tb = ctx->noise_tb;
   void *d_thr = ctx->d_noise_thr;
-  int *d_bits = (int *)ws_get(ctx, 9, sizeof(int) * count * (size_t)ctx->L);
+  int *d_bits = (int *)ws_get(ctx, WS_NOISE_BITS, sizeof(int) * count * (size_t)ctx->L);
   const int L = ctx->L, K = ctx->K, n = ctx->N_enc;
   hipStream_t st = S(stream);
   if (ctx->use_int) {  // the same composition on the integer arithmetic
@@ -536,16 +501,15 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
       ctx->d_crt_limbs = p;
     }
     const CrtLimbI *d_limbs = static_cast<const CrtLimbI *>(ctx->d_crt_limbs);
-    TabCopiesI tabs(ctx);
-    uint64_t *V = (uint64_t *)ws_get(ctx, 14, count * (size_t)L * K * n * sizeof(uint64_t));
+    uint64_t *V = (uint64_t *)ws_get(ctx, WS_STAGE_ROWS, count * (size_t)L * K * n * sizeof(uint64_t));
     const size_t lds = padded_len((size_t)n) * sizeof(uint64_t);
     const int thr = enc_threads(ctx->logN_enc);
     set_max_dyn_lds((const void *)decrypt_dot_kernel_int, (int)lds);
     set_max_dyn_lds((const void *)crt_decode_kernel_int, (int)lds);
     hipLaunchKernelGGL(decrypt_dot_kernel_int, dim3((unsigned)(count * L), K), dim3(thr), lds, st, d_enc, d_sk, V, K, ctx->logN_enc,
-                       tabs.d_coeff);
+                       ctx->d_coeff_tabs_i);
     hipLaunchKernelGGL(crt_decode_kernel_int, dim3((unsigned)(count * L)), dim3(thr), lds, st, V, d_rings, ctx->N, L, ctx->logN_enc,
-                       cc, d_limbs, ctx->d_index_map, tabs.d_plain, (const uint64_t *)d_thr, tb, d_bits);
+                       cc, d_limbs, ctx->d_index_map, ctx->d_plain_tabs_i, (const uint64_t *)d_thr, tb, d_bits);
     RS_HIP(hipGetLastError());
     RS_HIP(hipStreamSynchronize(st));
     return noise_verdict(ctx, d_bits, count, tb, d_rings != nullptr, h_budget);
@@ -592,18 +556,17 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
     ctx->d_crt_limbs = p;
   }
   const CrtLimb *d_limbs = static_cast<const CrtLimb *>(ctx->d_crt_limbs);
-  TabCopies tabs(ctx);
-  double *V = (double *)ws_get(ctx, 14, count * (size_t)L * K * n * sizeof(double));
+  double *V = (double *)ws_get(ctx, WS_STAGE_ROWS, count * (size_t)L * K * n * sizeof(double));
   const size_t lds = padded_len((size_t)n) * sizeof(double);
   const int thr = enc_threads(ctx->logN_enc);
   set_max_dyn_lds((const void *)decrypt_dot_kernel, (int)lds);
   set_max_dyn_lds((const void *)crt_decode_kernel, (int)lds);
   hipLaunchKernelGGL(decrypt_dot_kernel, dim3((unsigned)(count * L), K), dim3(thr), lds, st, d_enc, d_sk, V, K, ctx->logN_enc,
-                     tabs.d_coeff);
+                     ctx->d_coeff_tabs);
   hipLaunchKernelGGL(crt_decode_kernel, dim3((unsigned)(count * L)), dim3(thr), lds, st, V, d_rings, ctx->N, L, ctx->logN_enc,
-                     cc, d_limbs, ctx->d_index_map, tabs.d_plain, (const double *)d_thr, tb, d_bits);
+                     cc, d_limbs, ctx->d_index_map, ctx->d_plain_tabs, (const double *)d_thr, tb, d_bits);
   RS_HIP(hipGetLastError());
-  RS_HIP(hipStreamSynchronize(st));  // the table copies die with this call
+  RS_HIP(hipStreamSynchronize(st));
   return noise_verdict(ctx, d_bits, count, tb, d_rings != nullptr, h_budget);
 }
 
@@ -618,22 +581,20 @@ int rs_enc_encode(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_rings, si
   WsScope ws_scope(ctx, S(stream));
   hipStream_t st = S(stream);
   if (ctx->use_int) {
-    TabCopiesI tabs(ctx);
     const size_t lds = padded_len((size_t)ctx->N_enc) * sizeof(uint64_t);
     const int thr = std::max(enc_threads(ctx->logN_enc), ctx->N_enc / 16);
     set_max_dyn_lds((const void *)encode_kernel_int, (int)lds);
     hipLaunchKernelGGL(encode_kernel_int, dim3((unsigned)(count * ctx->L), ctx->K), dim3(thr), lds, st, d_rings, d_sk, d_enc, seed,
-                       ctx->N, ctx->L, ctx->K, ctx->logN_enc, ctx->d_index_map, tabs.d_plain, tabs.d_coeff);
+                       ctx->N, ctx->L, ctx->K, ctx->logN_enc, ctx->d_index_map, ctx->d_plain_tabs_i, ctx->d_coeff_tabs_i);
     RS_HIP(hipGetLastError());
     RS_HIP(hipStreamSynchronize(st));
     return RS_OK;
   }
-  TabCopies tabs(ctx);
   const size_t lds = padded_len((size_t)ctx->N_enc) * sizeof(double);
   const int thr = std::max(enc_threads(ctx->logN_enc), ctx->N_enc / 16);
   set_max_dyn_lds((const void *)encode_kernel, (int)lds);
   hipLaunchKernelGGL(encode_kernel, dim3((unsigned)(count * ctx->L), ctx->K), dim3(thr), lds, st, d_rings, d_sk, d_enc, seed,
-                     ctx->N, ctx->L, ctx->K, ctx->logN_enc, ctx->d_index_map, tabs.d_plain, tabs.d_coeff, tabs.d_q, tabs.d_Q);
+                     ctx->N, ctx->L, ctx->K, ctx->logN_enc, ctx->d_index_map, ctx->d_plain_tabs, ctx->d_coeff_tabs, ctx->d_qint, ctx->d_Qint);
   RS_HIP(hipGetLastError());
   RS_HIP(hipStreamSynchronize(st));
   RS_API_END
@@ -760,9 +721,6 @@ int rs_enc_deserialize(rs_ctx *ctx, const void *h_buf, size_t buf_bytes, uint64_
 // the same sparse kernel as row a14 on the transposed CSR.  Every value is a canonical residue of an
 // exact ring expression, hence bit-identical to the reference's order of operations.
 namespace rs {
-void r1cs_evaluate_run(rs_ctx *ctx, const rs_r1cs *cs, int which, int mode, const uint64_t *d_asg, uint64_t *d_out,
-                       hipStream_t st);
-
 // Per slot, with d_j = s - j:  Ht[j] = s^j (j <= m),  Zt = prod_j d_j,  and the Lagrange values
 //     u_j = c_j * prod_{i != j} d_i = c_j * (prod_{i < j} d_i) * (prod_{i > j} d_i)
 // by a backward pass (suffix products parked in U) and a forward pass (running prefix): no
@@ -854,22 +812,8 @@ int rs_instance_map_eval(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, ui
     }
   } guard;
   guard.p.push_back(D);
-  // slot-constant factors c_j = 1 / prod_{i != j} (j - i) = (-1)^(m-1-j) / (j! (m-1-j)!)
-  std::vector<double> hc((size_t)L * m);
-  std::vector<uint64_t> hci(ctx->use_int ? (size_t)L * m : 0);  // the same constants for the integer arithmetic
-  for (int l = 0; l < L; l++) {
-    const uint64_t q = ctx->q[l];
-    RS_REQUIRE(q > m, "ring prime too small for the evaluation domain");
-    std::vector<uint64_t> fact(m);
-    fact[0] = 1;
-    for (size_t j = 1; j < m; j++) fact[j] = host::mulmod(fact[j - 1], (uint64_t)j % q, q);
-    for (size_t j = 0; j < m; j++) {
-      uint64_t v = host::invmod(host::mulmod(fact[j], fact[m - 1 - j], q), q);
-      if ((m - 1 - j) & 1) v = v ? q - v : 0;
-      hc[(size_t)l * m + j] = host::balanced(v, q);
-      if (ctx->use_int) hci[(size_t)l * m + j] = HostArith<ModI>::konst(v, q);
-    }
-  }
+  std::vector<uint64_t> hc;  // slot-constant factors c_j [L][m], table constants of the context's arithmetic
+  RS_DISPATCH_ARITH(ctx, lagrange_constants<Mod>(ctx, m, hc), lagrange_constants<ModI>(ctx, m, hc));
   double *d_c = nullptr;
   RS_HIP(hipMalloc(&d_c, hc.size() * sizeof(double)));
   guard.p.push_back(d_c);
@@ -878,9 +822,7 @@ int rs_instance_map_eval(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, ui
   guard.p.push_back(d_hit);
   const unsigned hit0[2] = {0xFFFFFFFFu, 0u};
   unsigned hit[2];
-  static_assert(sizeof(double) == sizeof(uint64_t), "constant buffers are shared between the arithmetics");
-  RS_HIP(hipMemcpyAsync(d_c, ctx->use_int ? (const void *)hci.data() : (const void *)hc.data(), hc.size() * sizeof(double),
-                        hipMemcpyHostToDevice, st));
+  RS_HIP(hipMemcpyAsync(d_c, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice, st));
   RS_HIP(hipMemcpyAsync(d_hit, hit0, sizeof(hit0), hipMemcpyHostToDevice, st));
   if (ctx->use_int)
     hipLaunchKernelGGL(lagrange_kernel_int, dim3((unsigned)((SW + 255) / 256)), dim3(256), 0, st, d_s, d_Ht, D, d_Zt,

@@ -22,7 +22,7 @@
 // value-level result equals the reference's; the EMPTY result (all terms skipped) is reported
 // through the used-term counts.
 //
-// Kernels: msm_plain.hpp (plaintext rows), msm_mac.hpp (multiply-accumulate, reduction).  This file: scratch tables, launch
+// Kernels: msm_plain.hpp (plaintext rows), msm_mac.hpp (multiply-accumulate, reduction).  This file: launch
 // geometry, the tiled / host-streamed key loop (msm_run) and the extern "C" entry points.
 #include <algorithm>
 #include <cstring>
@@ -38,87 +38,23 @@ namespace rs {
 
 static int tile_threads(int logn) { return std::max(64, std::min(1024, (1 << logn) >> 3)); }
 
-struct MsmScratch {
-  void *d_plain_tabs = nullptr, *d_coeff_tabs = nullptr;  // device copies of the context's tables (NttTable or NttTableI)
-  uint64_t *d_Qint = nullptr;
-  uint64_t *d_ones_plain = nullptr;  // [L][N_enc]: batch encoding of the ring element (1, ..., 1), built at first use (slot-constant vectors)
-  void *d_coeff_tabs_f64 = nullptr;  // hybrid contexts: FP64 tables of the data primes beside the integer ones
-  // host-resident keys: copy stream and the events of the two staging buffers (copied: data landed; freed: its readers ran)
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_freed[2] = {nullptr, nullptr};
-  template <class M>
-  const NttTableT<typename ArithOf<M>::T, M> *plain() const {
-    return static_cast<const NttTableT<typename ArithOf<M>::T, M> *>(d_plain_tabs);
-  }
-  template <class M>
-  const NttTableT<typename ArithOf<M>::T, M> *coeff() const {
-    return static_cast<const NttTableT<typename ArithOf<M>::T, M> *>(d_coeff_tabs);
-  }
-};
-
-static std::map<rs_ctx *, MsmScratch> g_scratch;
-static std::mutex g_scratch_mu;
-
-template <class Table>
-static void *copy_tables(const Table *h, int n) {
-  void *d = nullptr;
-  RS_HIP(hipMalloc(&d, sizeof(Table) * n));
-  RS_HIP(hipMemcpy(d, h, sizeof(Table) * n, hipMemcpyHostToDevice));
-  return d;
-}
-static MsmScratch &scratch_for(rs_ctx *ctx) {
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  auto it = g_scratch.find(ctx);
-  if (it != g_scratch.end()) return it->second;
-  MsmScratch sc;
-  if (ctx->use_int) {
-    sc.d_plain_tabs = copy_tables(ctx->plain_i, ctx->L);
-    sc.d_coeff_tabs = copy_tables(ctx->coeff_i, ctx->K);
-    if (ctx->hybrid) sc.d_coeff_tabs_f64 = copy_tables(ctx->coeff, ctx->K);
-  } else {
-    sc.d_plain_tabs = copy_tables(ctx->plain, ctx->L);
-    sc.d_coeff_tabs = copy_tables(ctx->coeff, ctx->K);
-  }
-  RS_HIP(hipMalloc(&sc.d_Qint, sizeof(uint64_t) * ctx->K));
-  RS_HIP(hipMemcpy(sc.d_Qint, ctx->Q, sizeof(uint64_t) * ctx->K, hipMemcpyHostToDevice));
-  return g_scratch[ctx] = sc;
-}
-void msm_scratch_release(rs_ctx *ctx) {
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  auto it = g_scratch.find(ctx);
-  if (it == g_scratch.end()) return;
-  (void)hipFree(it->second.d_plain_tabs);
-  (void)hipFree(it->second.d_coeff_tabs);
-  (void)hipFree(it->second.d_Qint);
-  if (it->second.d_ones_plain) (void)hipFree(it->second.d_ones_plain);
-  if (it->second.d_coeff_tabs_f64) (void)hipFree(it->second.d_coeff_tabs_f64);
-  if (it->second.copy_stream) {
-    (void)hipStreamDestroy(it->second.copy_stream);
-    for (int b = 0; b < 2; b++) {
-      (void)hipEventDestroy(it->second.ev_copied[b]);
-      (void)hipEventDestroy(it->second.ev_freed[b]);
-    }
-  }
-  g_scratch.erase(it);
-}
-
 template <int NG, int NC, int PAIRS, class M>
-static void launch_mac(rs_ctx *ctx, const MacArgs &a, const MsmScratch &sc, hipStream_t st) {
+static void launch_mac(rs_ctx *ctx, const MacArgs &a, hipStream_t st) {
   const size_t lds = padded_len((size_t)ctx->N_enc) * sizeof(double);
   const int rows = a.n_chunks * ctx->L;
   const unsigned blocks = (unsigned)(((rows + 7) / 8) * 8 * ctx->K);
   set_max_dyn_lds((const void *)mac_kernel<NG, NC, PAIRS, M>, (int)lds);
   hipLaunchKernelGGL((mac_kernel<NG, NC, PAIRS, M>), dim3(blocks), dim3(tile_threads(ctx->logN_enc)), lds, st, a, ctx->L,
-                     ctx->K, ctx->logN_enc, sc.template coeff<M>());
+                     ctx->K, ctx->logN_enc, CtxArith<M>::d_coeff(ctx));
   RS_HIP(hipGetLastError());
 }
 
-static void launch_mac_v2(rs_ctx *ctx, const MacArgs2 &a, const MsmScratch &sc, hipStream_t st) {
+static void launch_mac_v2(rs_ctx *ctx, const MacArgs2 &a, hipStream_t st) {
   const size_t lds = (padded_len((size_t)ctx->N_enc) + (size_t)ctx->N_enc) * sizeof(double);
   const int rows = a.n_chunks * ctx->L;
   const unsigned blocks = (unsigned)(((rows + 7) / 8) * 8 * ctx->K);
   set_max_dyn_lds((const void *)mac_kernel_v2<512>, (int)lds);
-  hipLaunchKernelGGL(mac_kernel_v2<512>, dim3(blocks), dim3(512), lds, st, a, ctx->L, ctx->K, ctx->logN_enc, sc.coeff<Mod>());
+  hipLaunchKernelGGL(mac_kernel_v2<512>, dim3(blocks), dim3(512), lds, st, a, ctx->L, ctx->K, ctx->logN_enc, ctx->d_coeff_tabs);
   RS_HIP(hipGetLastError());
 }
 
@@ -138,11 +74,10 @@ static uint32_t fwd_reduce_mask_from(uint64_t p, int logn, double b0, double *en
   *end_bound = B * (double)p;  // bound of the spectrum values
   return mask;
 }
-static void launch_mac_v3(rs_ctx *ctx, const MacArgs3 &a, const MsmScratch &sc, hipStream_t st) {
+static void launch_mac_v3(rs_ctx *ctx, const MacArgs3 &a, hipStream_t st) {
   const size_t lds = (size_t)(2 * (4096 + 256) + 1024) * sizeof(double);  // two tiles + round-2 twiddles
   const unsigned rows = (unsigned)ctx->L * (unsigned)a.n_chunks;  // (chunk, limb), spread over the XCDs
-  // FP64 tables of the data primes: the context's own, or -- hybrid context -- the copies kept beside the integer tables
-  const NttTable *tabs = ctx->use_int ? static_cast<const NttTable *>(sc.d_coeff_tabs_f64) : sc.coeff<Mod>();
+  const NttTable *tabs = ctx->d_coeff_tabs;  // FP64 tables of the data primes: a hybrid context keeps them beside the integer tables
   const unsigned parts = (unsigned)ctx->N_enc / 4096u;  // workgroups per (limb, prime): halves at 8192 points, quarters at 16384
   const unsigned blocks = ((rows + 7) / 8) * 8 * parts * (unsigned)ctx->K * (unsigned)a.n_groups;
   if (ctx->N_enc == 16384) {
@@ -158,10 +93,10 @@ static void launch_mac_v3(rs_ctx *ctx, const MacArgs3 &a, const MsmScratch &sc, 
   RS_HIP(hipGetLastError());
 }
 
-static void launch_mac_v4(rs_ctx *ctx, const MacArgs4 &a, bool paired, const MsmScratch &sc, hipStream_t st) {
+static void launch_mac_v4(rs_ctx *ctx, const MacArgs4 &a, bool paired, hipStream_t st) {
   const size_t lds = (size_t)2 * (4096 + 512) * sizeof(double);  // two tiles
   const unsigned rows = (unsigned)ctx->L * (unsigned)a.n_chunks;
-  const NttTable *tabs = ctx->use_int ? static_cast<const NttTable *>(sc.d_coeff_tabs_f64) : sc.coeff<Mod>();
+  const NttTable *tabs = ctx->d_coeff_tabs;
   const unsigned parts = (unsigned)ctx->N_enc / 4096u;
   const unsigned blocks = ((rows + 7) / 8) * 8 * parts * (unsigned)ctx->K * (unsigned)a.n_groups;
 #define RS_MAC4_LAUNCH(LOGN_, PAIRED_)                                                                                          \
@@ -185,8 +120,6 @@ __global__ void __launch_bounds__(256) broadcast_rows_kernel(const uint64_t *__r
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) out[i] = vals[i / (size_t)N];
 }
-void batch_encode_run(rs_ctx *ctx, const uint64_t *d_rings, uint64_t *d_plain, size_t count, hipStream_t st);
-
 // Core grouped MSM.  addends: optional per-output (n_crs * n_groups) device pointers to encoding
 // elements added to the result (pk.alpha / pk.beta of groth16.tcc:95,103).
 // crs_window != 0: every CRS vector is stored as `crs_window` consecutive elements and logical
@@ -202,7 +135,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   RS_REQUIRE(n_crs * n_groups <= 12, "too many outputs");
   const int L = ctx->L, K = ctx->K, n = ctx->N_enc;
   const size_t enc_words = ctx->enc_words();
-  MsmScratch &sc = scratch_for(ctx);
+  MsmState &sc = ctx->msm;
 
   // group bookkeeping
   PlainArgs pa;
@@ -224,10 +157,10 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   unsigned *d_nz = nullptr;
   uint8_t *d_kinds = nullptr;
   if (nz_total) {
-    d_nz = (unsigned *)ws_get(ctx, 2, nz_total * sizeof(unsigned));
+    d_nz = (unsigned *)ws_get(ctx, WS_MSM_USED, nz_total * sizeof(unsigned));
     RS_HIP(hipMemsetAsync(d_nz, 0, nz_total * sizeof(unsigned), st));
   }
-  if (kinds_total) d_kinds = (uint8_t *)ws_get(ctx, 3, kinds_total);
+  if (kinds_total) d_kinds = (uint8_t *)ws_get(ctx, WS_MSM_KINDS, kinds_total);
   // Slot-constant vectors (rs_msm_vec::slot_const: [T][L] values).  The generic plaintext kernel multiplies the value into
   // the plaintext of (1, ..., 1); the wide 8192-point kernel has no such path: there the rows are expanded into a workspace.
   bool any_sc = false;
@@ -237,10 +170,10 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   for (int v = 0; v < n_vecs; v++) coeff_ptr[v] = vecs[v].d_coeff;
   if (any_sc && sc_native && !sc.d_ones_plain) {
     const size_t rw = ctx->ring_words();
-    uint64_t *ones = (uint64_t *)ws_get(ctx, 14, rw * sizeof(uint64_t));
+    uint64_t *ones = (uint64_t *)ws_get(ctx, WS_STAGE_ROWS, rw * sizeof(uint64_t));
     hipLaunchKernelGGL(fill_value_kernel, dim3((unsigned)((rw + 255) / 256)), dim3(256), 0, st, ones, rw, 1ull);
     RS_HIP(hipMalloc(&sc.d_ones_plain, (size_t)L * n * sizeof(uint64_t)));
-    batch_encode_run(ctx, ones, sc.d_ones_plain, 1, st);  // sc is the context's entry itself (scratch_for returns a reference)
+    batch_encode_run(ctx, ones, sc.d_ones_plain, 1, st);
     // the table is cached for the life of the context and read by later calls on ANY stream: it must be complete
     // before its pointer is visible to them (once per context)
     RS_HIP(hipStreamSynchronize(st));
@@ -248,7 +181,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   if (any_sc && !sc_native) {
     size_t rows = 0;
     for (int v = 0; v < n_vecs; v++) rows += vecs[v].slot_const ? vecs[v].T : 0;
-    uint64_t *buf = (uint64_t *)ws_get(ctx, 14, std::max<size_t>(1, rows) * ctx->ring_words() * sizeof(uint64_t));
+    uint64_t *buf = (uint64_t *)ws_get(ctx, WS_STAGE_ROWS, std::max<size_t>(1, rows) * ctx->ring_words() * sizeof(uint64_t));
     size_t at = 0;
     for (int v = 0; v < n_vecs; v++)
       if (vecs[v].slot_const && vecs[v].T) {
@@ -316,13 +249,11 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
       tile_terms = std::min(p2, crs_window);  // may no longer divide the window: issue_copy splits a tile at the wrap
     }
     stage_words = tile_terms * enc_words;
-    stage = (uint64_t *)ws_get(ctx, 7, (size_t)2 * n_crs * stage_words * sizeof(uint64_t));
-    if (!sc.copy_stream) {
-      RS_HIP(hipStreamCreateWithFlags(&sc.copy_stream, hipStreamNonBlocking));
-      for (int b = 0; b < 2; b++) {
-        RS_HIP(hipEventCreateWithFlags(&sc.ev_copied[b], hipEventDisableTiming));
-        RS_HIP(hipEventCreateWithFlags(&sc.ev_freed[b], hipEventDisableTiming));
-      }
+    stage = (uint64_t *)ws_get(ctx, WS_SMALL, (size_t)2 * n_crs * stage_words * sizeof(uint64_t));
+    if (!sc.copy_stream) RS_HIP(hipStreamCreateWithFlags(&sc.copy_stream, hipStreamNonBlocking));
+    for (int b = 0; b < 2; b++) {  // each by its own null test: a call that failed half way is completed by the next
+      if (!sc.ev_copied[b]) RS_HIP(hipEventCreateWithFlags(&sc.ev_copied[b], hipEventDisableTiming));
+      if (!sc.ev_freed[b]) RS_HIP(hipEventCreateWithFlags(&sc.ev_freed[b], hipEventDisableTiming));
     }
     // the staging buffers may still be read by an earlier call on another stream: order the copy stream after `st`
     RS_HIP(hipEventRecord(sc.ev_freed[0], st));
@@ -365,8 +296,8 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     if (n_chunks >= step && (size_t)((n_chunks + step - 1) / step * step) <= tile_terms) n_chunks = (n_chunks + step - 1) / step * step;
   }
   if (Tmax == 0) n_chunks = 1;
-  Lift *d_C = (Lift *)ws_get(ctx, 0, std::max<size_t>(256, tile_terms * c_bytes_per_term));
-  uint64_t *d_partial = (uint64_t *)ws_get(ctx, 1, (size_t)n_chunks * n_sets * enc_words * sizeof(uint64_t));
+  Lift *d_C = (Lift *)ws_get(ctx, WS_MSM_ROWS, std::max<size_t>(256, tile_terms * c_bytes_per_term));
+  uint64_t *d_partial = (uint64_t *)ws_get(ctx, WS_MSM_PARTIAL, (size_t)n_chunks * n_sets * enc_words * sizeof(uint64_t));
   const size_t lds = padded_len((size_t)n) * sizeof(double);
   const int thr = tile_threads(ctx->logN_enc);
   const bool big = n > 8192;  // one accumulator set per MAC launch
@@ -434,7 +365,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
                                wl);                                              \
     hipLaunchKernelGGL((plain_center_wide_kernel<MULTI_, PAIRED_, NE_, LIN_>), grid, dim3(256), wl, st, pa,                   \
                        reinterpret_cast<double *>(d_C), (unsigned long long)t0, (unsigned long long)tile_terms,               \
-                       (unsigned long long)tt, n_groups, ctx->N, L, ctx->d_index_map, sc.plain<Mod>(), twp);                  \
+                       (unsigned long long)tt, n_groups, ctx->N, L, ctx->d_index_map, ctx->d_plain_tabs, twp);                  \
   } while (0)
 #define RS_PLAIN_WIDE(MULTI_, PAIRED_)                                  \
   do {                                                                  \
@@ -456,11 +387,11 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     } else if (plain16)
       hipLaunchKernelGGL((plain_center_kernel<16, 0, M>), dim3((unsigned)tt, L, n_groups), dim3(plain_thr), lds, st, pa, d_C,
                          (unsigned long long)t0, (unsigned long long)tile_terms, ctx->N, L, ctx->logN_enc,
-                         ctx->d_index_map, sc.template plain<M>(), hybrid ? 1 : 0);
+                         ctx->d_index_map, CtxArith<M>::d_plain(ctx), hybrid ? 1 : 0);
     else
       hipLaunchKernelGGL((plain_center_kernel<8, 0, M>), dim3((unsigned)tt, L, n_groups), dim3(thr), lds, st, pa, d_C,
                          (unsigned long long)t0, (unsigned long long)tile_terms, ctx->N, L, ctx->logN_enc,
-                         ctx->d_index_map, sc.template plain<M>(), hybrid ? 1 : 0);
+                         ctx->d_index_map, CtxArith<M>::d_plain(ctx), hybrid ? 1 : 0);
     }
     RS_HIP(hipGetLastError());
     MacArgs base;
@@ -495,13 +426,13 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
                      (double)tt * NC * (double)enc_words * 8.0 + units * nd * 8.0 / K + (double)NG * NC * (double)enc_words * 8.0,
                      units * (ntt_fp64(nd, logn_d) + NC * 15.0 * nd));
       if (big)
-        launch_mac<1, 1, 8, M>(ctx, a, sc, st);
+        launch_mac<1, 1, 8, M>(ctx, a, st);
       else if (NG == 2 && NC == 1)
-        launch_mac<2, 1, 4, M>(ctx, a, sc, st);
+        launch_mac<2, 1, 4, M>(ctx, a, st);
       else if (NG == 1 && NC == 2)
-        launch_mac<1, 2, 4, M>(ctx, a, sc, st);
+        launch_mac<1, 2, 4, M>(ctx, a, st);
       else
-        launch_mac<1, 1, 4, M>(ctx, a, sc, st);
+        launch_mac<1, 1, 4, M>(ctx, a, st);
     };
     // streaming kernel, one accumulator set (CRS vector c, group g) per launch.  With two CRS
     // vectors (Rinocchio's s_pows / alpha_s_pows) the plaintext transform is repeated per vector:
@@ -543,7 +474,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
             }
             ProfScope prof(ctx, st, n == 16384 ? "mac_kernel_v4<14, false>" : (paired ? "mac_kernel_v4<13, true>" : "mac_kernel_v4<13, false>"), (double)tmax * 2.0 * (double)enc_words * 8.0 + terms * (double)L * nd * 8.0 + 2.0 * ng * (double)enc_words * 8.0,
                            terms * L * K * (ntt_fp64(nd, logn_d) + 8.0 * nd / 2.0 + 2.0 * 15.0 * nd));
-            launch_mac_v4(ctx, a4, paired, sc, st);
+            launch_mac_v4(ctx, a4, paired, st);
           }
         } else
         // chunks: two workgroups per CU in one wave of workgroups (512), shared by the groups of a launch
@@ -580,7 +511,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
             // the accumulator sets written once
             ProfScope prof(ctx, st, n == 16384 ? "mac_kernel_v3<false, 14>" : "mac_kernel_v3", (double)tmax * (double)enc_words * 8.0 + terms * (double)L * nd * 8.0 + ng * (double)enc_words * 8.0,
                            terms * L * K * (ntt_fp64(nd, logn_d) + 8.0 * nd / 2.0 + 15.0 * nd));
-            launch_mac_v3(ctx, a3, sc, st);
+            launch_mac_v3(ctx, a3, st);
           }
       }
     } else if (v2) {
@@ -602,7 +533,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
         const double terms = (double)a2.terms;
         ProfScope prof(ctx, st, "mac_kernel_v2", terms * ((double)enc_words * 8.0 + (double)L * nd * 8.0) + (double)enc_words * 8.0,
                        terms * L * K * (ntt_fp64(nd, logn_d) + 15.0 * nd));
-        launch_mac_v2(ctx, a2, sc, st);
+        launch_mac_v2(ctx, a2, st);
       }
     } else if (big) {  // one (crs, group) pair per launch
       for (int c = 0; c < n_crs; c++)
@@ -638,7 +569,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     const size_t total = (size_t)n_sets * enc_words;
     const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 16);
     hipLaunchKernelGGL(reduce_kernel, dim3(blocks), dim3(256), 0, st, d_partial, d_out, ra, n_chunks, n_sets, enc_words, n,
-                       K, sc.d_Qint);
+                       K, ctx->d_Qint);
     RS_HIP(hipGetLastError());
   }
   if (h_used) {
@@ -657,7 +588,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
 
 void msm_run(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
              int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
-             size_t crs_window, const MsmLin *lin = nullptr, bool crs_on_host = false) {
+             size_t crs_window, const MsmLin *lin, bool crs_on_host) {
   RS_DISPATCH_ARITH(ctx, (msm_run_arith<Mod>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host)),
                     (msm_run_arith<ModI>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host)));
 }
@@ -667,16 +598,15 @@ bool msm_supports_lin(const rs_ctx *ctx) {
 }
 void batch_encode_run(rs_ctx *ctx, const uint64_t *d_rings, uint64_t *d_plain, size_t count, hipStream_t st) {
   if (!count) return;
-  MsmScratch &sc = scratch_for(ctx);
   const size_t lds = padded_len((size_t)ctx->N_enc) * sizeof(double);
   if (ctx->use_int) {
     set_max_dyn_lds((const void *)batch_encode_kernel<ModI>, (int)lds);
     hipLaunchKernelGGL(batch_encode_kernel<ModI>, dim3((unsigned)count, ctx->L), dim3(tile_threads(ctx->logN_enc)), lds, st, d_rings, d_plain,
-                       ctx->N, ctx->L, ctx->logN_enc, ctx->d_index_map, sc.plain<ModI>());
+                       ctx->N, ctx->L, ctx->logN_enc, ctx->d_index_map, ctx->d_plain_tabs_i);
   } else {
     set_max_dyn_lds((const void *)batch_encode_kernel<Mod>, (int)lds);
     hipLaunchKernelGGL(batch_encode_kernel<Mod>, dim3((unsigned)count, ctx->L), dim3(tile_threads(ctx->logN_enc)), lds, st, d_rings, d_plain,
-                       ctx->N, ctx->L, ctx->logN_enc, ctx->d_index_map, sc.plain<Mod>());
+                       ctx->N, ctx->L, ctx->logN_enc, ctx->d_index_map, ctx->d_plain_tabs);
   }
   RS_HIP(hipGetLastError());
 }
@@ -684,13 +614,12 @@ void batch_encode_run(rs_ctx *ctx, const uint64_t *d_rings, uint64_t *d_plain, s
 void enc_add_run(rs_ctx *ctx, uint64_t *dst, const uint64_t *x, const uint64_t *y, size_t count, hipStream_t st) {
   const size_t words = count * ctx->enc_words();
   if (!words) return;
-  MsmScratch &sc = scratch_for(ctx);
   const size_t pairs = words / 2;  // N_enc is even: whole 16-byte words
   const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((pairs + 2047) / 2048, 256 * 8));
   if (pairs * 16 >= ((size_t)64 << 20))  // non-temporal accesses for operands beyond the caches
-    hipLaunchKernelGGL(enc_add_kernel<true>, dim3(blocks), dim3(256), 0, st, dst, x, y, pairs, ctx->logN_enc, ctx->K, sc.d_Qint);
+    hipLaunchKernelGGL(enc_add_kernel<true>, dim3(blocks), dim3(256), 0, st, dst, x, y, pairs, ctx->logN_enc, ctx->K, ctx->d_Qint);
   else
-    hipLaunchKernelGGL(enc_add_kernel<false>, dim3(blocks), dim3(256), 0, st, dst, x, y, pairs, ctx->logN_enc, ctx->K, sc.d_Qint);
+    hipLaunchKernelGGL(enc_add_kernel<false>, dim3(blocks), dim3(256), 0, st, dst, x, y, pairs, ctx->logN_enc, ctx->K, ctx->d_Qint);
   RS_HIP(hipGetLastError());
 }
 
@@ -753,7 +682,7 @@ int rs_enc_mul_ring(rs_ctx *ctx, uint64_t *d_enc, const uint64_t *d_ring, size_t
   RS_API_BEGIN_CTX(ctx)
   RS_REQUIRE(ctx && d_enc && d_ring, "null argument");
   WsScope ws_scope(ctx, S(stream));
-  uint64_t *tmp = (uint64_t *)ws_get(ctx, 4, ctx->enc_words() * sizeof(uint64_t));
+  uint64_t *tmp = (uint64_t *)ws_get(ctx, WS_SIDE, ctx->enc_words() * sizeof(uint64_t));
   for (size_t k = 0; k < count; k++) {
     rs_msm_vec v{d_ring + k * ctx->ring_words(), nullptr, 1, 0};
     const uint64_t *crs[1] = {d_enc + k * ctx->enc_words()};
@@ -769,9 +698,8 @@ int rs_enc_reduce(rs_ctx *ctx, uint64_t *d_enc, size_t count, rs_stream stream) 
   RS_REQUIRE(ctx && d_enc, "null argument");
   const size_t words = count * ctx->enc_words();
   if (words) {
-    MsmScratch &sc = scratch_for(ctx);
-    const unsigned blocks = (unsigned)std::min<size_t>((words + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(enc_reduce_kernel, dim3(blocks), dim3(256), 0, S(stream), d_enc, words, ctx->N_enc, ctx->K, sc.d_Qint);
+      const unsigned blocks = (unsigned)std::min<size_t>((words + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(enc_reduce_kernel, dim3(blocks), dim3(256), 0, S(stream), d_enc, words, ctx->N_enc, ctx->K, ctx->d_Qint);
     RS_HIP(hipGetLastError());
   }
   RS_API_END

@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(256) rows_nonzero_kernel(const uint64_t *__res
 // Boost's polynomial normalisation: length after stripping trailing coefficients equal to RingT(0)
 static size_t normalised_len(rs_ctx *ctx, const uint64_t *d, size_t n, hipStream_t st) {
   if (n == 0) return 0;
-  unsigned *flags = (unsigned *)ws_get(ctx, 7, std::max<size_t>(256, n * 4));
+  unsigned *flags = (unsigned *)ws_get(ctx, WS_SMALL, std::max<size_t>(256, n * 4));
   RS_HIP(hipMemsetAsync(flags, 0, n * 4, st));
   hipLaunchKernelGGL(rows_nonzero_kernel, dim3((unsigned)n), dim3(256), 0, st, d, ctx->ring_words(), flags);
   std::vector<unsigned> h(n);

@@ -6,19 +6,6 @@
 #include "rs_internal.hpp"
 
 namespace rs {
-void msm_run(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
-             int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
-             size_t crs_window, const MsmLin *lin = nullptr, bool crs_on_host = false);
-bool msm_supports_lin(const rs_ctx *ctx);
-void batch_encode_run(rs_ctx *ctx, const uint64_t *d_rings, uint64_t *d_plain, size_t count, hipStream_t st);
-bool witness_io_shortcut(const rs_r1cs *cs);
-void enc_add_run(rs_ctx *ctx, uint64_t *dst, const uint64_t *x, const uint64_t *y, size_t count, hipStream_t st);
-const uint64_t *witness_Z_rows(rs_ctx *ctx, size_t m);
-void witness_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_asg, const uint64_t *d1, const uint64_t *d2,
-                 const uint64_t *d3, uint64_t *const outs[7], uint64_t *h_Z, hipStream_t st, int slot0 = 0, int nslots = -1,
-                 bool compact = false, const size_t (*rows)[2] = nullptr);
-void msm_scratch_release(rs_ctx *ctx);
-
 __global__ void __launch_bounds__(256) fill_ones_kernel(uint64_t *p, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 1;
@@ -112,7 +99,7 @@ int rs_groth16_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *
   PhaseTimer pt(ctx, st);
   pt.mark(0);
   // witness map (groth16.tcc:82-84: d1 = d2 = d3 = 0); C_io / C_mid are not consumed by the prover
-  uint64_t *wbuf = (uint64_t *)ws_get(ctx, 8, (5 * m + 1) * rw * sizeof(uint64_t));
+  uint64_t *wbuf = (uint64_t *)ws_get(ctx, WS_PROVER_VECS, (5 * m + 1) * rw * sizeof(uint64_t));
   uint64_t *A_io = wbuf, *A_mid = wbuf + m * rw, *B_io = wbuf + 2 * m * rw, *B_mid = wbuf + 3 * m * rw, *H = wbuf + 4 * m * rw;
   // The io vectors are linear forms of the primary inputs (witness.hip): when the inner product can take them in that
   // form (MsmLin) they are neither written by the witness map nor read and transformed by the inner product.
@@ -197,7 +184,7 @@ int rs_rinocchio_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_
   memset(&ctx->timings, 0, sizeof(ctx->timings));
   PhaseTimer pt(ctx, st);
   pt.mark(0);
-  uint64_t *wbuf = (uint64_t *)ws_get(ctx, 8, (4 * m + 1) * rw * sizeof(uint64_t));
+  uint64_t *wbuf = (uint64_t *)ws_get(ctx, WS_PROVER_VECS, (4 * m + 1) * rw * sizeof(uint64_t));
   uint64_t *A_mid = wbuf, *B_mid = wbuf + m * rw, *C_mid = wbuf + 2 * m * rw, *H = wbuf + 3 * m * rw;
   uint64_t *outs[7] = {nullptr, nullptr, nullptr, A_mid, B_mid, C_mid, H};
   witness_run(ctx, cs, d_assignment, d_d1, d_d2, d_d3, outs, nullptr, st);
@@ -207,7 +194,7 @@ int rs_rinocchio_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_
   const uint64_t *dZ = witness_Z_rows(ctx, m);
   pt.mark(1);
   // the ten inner products of rinocchio.tcc:106-163 in one grouped pass over both CRS vectors
-  uint64_t *mo = (uint64_t *)ws_get(ctx, 10, 11 * ew * sizeof(uint64_t));  // [2][5] + tmp
+  uint64_t *mo = (uint64_t *)ws_get(ctx, WS_RINOCCHIO_OUT, 11 * ew * sizeof(uint64_t));  // [2][5] + tmp
   uint64_t *tmp = mo + 10 * ew;
   std::vector<uint8_t> zkinds(m + 1, RS_KIND_POLY);
   zkinds[m] = RS_KIND_ONE;  // leading coefficient of Z is the RingElem Scalar 1 (evaluation_domain.tcc:55-58)
@@ -268,19 +255,15 @@ int rs_rinocchio_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_
 int rs_fill_uniform(rs_ctx *ctx, uint64_t *d_dst, size_t count, int layout, uint64_t seed, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
   RS_REQUIRE(ctx && d_dst && (layout == 0 || layout == 1), "bad argument");
-  WsScope ws_scope(ctx, S(stream));
-  uint64_t *mods = (uint64_t *)ws_get(ctx, 11, sizeof(uint64_t) * (RS_MAX_L + RS_MAX_K));
-  RS_HIP(hipMemcpyAsync(mods, ctx->q, sizeof(uint64_t) * ctx->L, hipMemcpyHostToDevice, S(stream)));
-  RS_HIP(hipMemcpyAsync(mods + RS_MAX_L, ctx->Q, sizeof(uint64_t) * ctx->K, hipMemcpyHostToDevice, S(stream)));
   const size_t words = count * (layout == 0 ? ctx->ring_words() : ctx->enc_words());
   if (words) {
     const unsigned blocks = (unsigned)std::min<size_t>((words + 255) / 256, 256 * 32);
     if (layout == 0)
       hipLaunchKernelGGL(fill_uniform_kernel, dim3(blocks), dim3(256), 0, S(stream), d_dst, words, (size_t)ctx->N, ctx->L,
-                         mods, seed);
+                         ctx->d_qint, seed);
     else
       hipLaunchKernelGGL(fill_uniform_kernel, dim3(blocks), dim3(256), 0, S(stream), d_dst, words, (size_t)ctx->N_enc,
-                         ctx->K, mods + RS_MAX_L, seed);
+                         ctx->K, ctx->d_Qint, seed);
     RS_HIP(hipGetLastError());
   }
   RS_API_END

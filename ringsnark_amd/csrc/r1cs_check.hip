@@ -163,7 +163,7 @@ int rs_r1cs_check(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_assignment, 
     hipStream_t st = S(stream);
     WsScope ws_scope(ctx, st);
     // workspace: the report words, then (unless the caller brought them) the flag bytes
-    char *ws = (char *)ws_get(ctx, 7, std::max<size_t>(256, 64 + (d_row_flags ? 0 : m)));
+    char *ws = (char *)ws_get(ctx, WS_SMALL, std::max<size_t>(256, 64 + (d_row_flags ? 0 : m)));
     unsigned long long *rep = (unsigned long long *)ws;
     uint8_t *flags = d_row_flags ? d_row_flags : (uint8_t *)(ws + 64);
     RS_HIP(hipMemsetAsync(rep, 0, sizeof(unsigned long long) * CHECK_WORDS, st));

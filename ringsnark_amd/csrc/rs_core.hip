@@ -6,14 +6,14 @@
 #include "ntt_core.hpp"
 #include "ntt_wide.hpp"
 #include "rs_internal.hpp"
-#include "witness_plan.hpp"
 
 namespace rs {
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string &m) { g_last_error = m; }
 
-void *ws_get(rs_ctx *ctx, int slot, size_t bytes) {
+void *ws_get(rs_ctx *ctx, WsSlot slot, size_t bytes) {
+  static_assert(WS_COUNT <= 32, "rs_ctx::ws_touched is a 32-bit mask");
   DeviceBuf &b = ctx->ws[slot];
   if (b.used && b.last_stream != ctx->cur_stream) {
     // the previous user ran on another stream: order this call's work after it (device side)
@@ -55,7 +55,7 @@ ProfScope::~ProfScope() {
   if (idx >= 0) (void)hipEventRecord(ctx->prof[idx].e1, st);
 }
 WsScope::~WsScope() {
-  for (int k = 0; k < 16; k++) {
+  for (int k = 0; k < WS_COUNT; k++) {
     if (!((ctx->ws_touched >> k) & 1u)) continue;
     DeviceBuf &b = ctx->ws[k];
     if (!b.last_use && hipEventCreateWithFlags(&b.last_use, hipEventDisableTiming) != hipSuccess) {
@@ -120,11 +120,15 @@ uint32_t inv_reduce_mask(uint64_t p, int logn, int u0) {
   return mask;
 }
 
+// a device copy of h[0..n); nothing stays allocated when the copy fails
 template <class T>
-static T *upload_words(const std::vector<T> &h) {
+static T *upload(const T *h, size_t n) {
   T *d = nullptr;
-  RS_HIP(hipMalloc(&d, h.size() * sizeof(T)));
-  RS_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+  RS_HIP(hipMalloc(&d, n * sizeof(T)));
+  if (hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    throw Error(RS_ERR_HIP, "upload of a table of the context failed");
+  }
   return d;
 }
 
@@ -147,8 +151,13 @@ NttTableT<typename HostArith<M>::T, M> make_negacyclic_table(uint64_t p, int log
     itw[k] = HostArith<M>::konst(invmod(pw, p), p);
     pw = mulmod(pw, psi, p);
   }
-  t.d_tw = upload_words(tw);
-  t.d_itw = upload_words(itw);
+  t.d_tw = upload(tw.data(), n);
+  try {
+    t.d_itw = upload(itw.data(), n);
+  } catch (...) {
+    free_table(t);
+    throw;
+  }
   t.ninv = HostArith<M>::konst(invmod((uint64_t)n % p, p), p);
   t.fwd_red_mask = fwd_reduce_mask(p, logn);
   t.inv_red_mask = inv_reduce_mask(p, logn);
@@ -156,6 +165,20 @@ NttTableT<typename HostArith<M>::T, M> make_negacyclic_table(uint64_t p, int log
 }
 template NttTable make_negacyclic_table<Mod>(uint64_t, int);
 template NttTableI make_negacyclic_table<ModI>(uint64_t, int);
+
+// rs_ctx_create: the tables of the primes p[0..n) into the context's array `tabs` (one at a time: rs_ctx_destroy frees what
+// a failed build leaves), their device copy and, unless d_mods is null, the device array of their moduli
+template <class M>
+static void build_tables(const uint64_t *p, int n, int logn, NttTableT<typename HostArith<M>::T, M> *tabs,
+                         NttTableT<typename HostArith<M>::T, M> **d_tabs, M **d_mods) {
+  std::vector<M> mods(n);
+  for (int i = 0; i < n; i++) {
+    tabs[i] = make_negacyclic_table<M>(p[i], logn);
+    mods[i] = tabs[i].mod;
+  }
+  *d_tabs = upload(tabs, (size_t)n);
+  if (d_mods) *d_mods = upload(mods.data(), (size_t)n);
+}
 
 // ---------------------------------------------------------------------------------------------
 // a4: batched negacyclic NTT.  One workgroup per polynomial; global <-> LDS traffic is one
@@ -673,7 +696,11 @@ int rs_ctx_create(int device, int N, int L, const uint64_t *q, int N_enc, int K,
     if (p >= (1ull << 50)) any_big = true;  // beyond the exact-FP64 range: the whole context runs on Montgomery integers
     for (int k = 0; k < i; k++) RS_REQUIRE(p != (k < L ? q[k] : Q[k - L]), "moduli must be pairwise distinct");
   }
-  rs_ctx *c = new rs_ctx();
+  struct Holder {  // destroys a partly built context when anything below throws
+    rs_ctx *p;
+    ~Holder() { rs_ctx_destroy(p); }
+  } holder{new rs_ctx()};
+  rs_ctx *c = holder.p;
   c->device = device;
   c->N = N;
   c->L = L;
@@ -684,43 +711,23 @@ int rs_ctx_create(int device, int N, int L, const uint64_t *q, int N_enc, int K,
   c->use_int = any_big || g_tune.force_int_arith;
   for (int i = 0; i < L; i++) c->q[i] = q[i];
   for (int j = 0; j < K; j++) c->Q[j] = Q[j];
-  if (c->use_int) {
-    std::vector<ModI> qm(L), Qm(K);
-    for (int i = 0; i < L; i++) {
-      c->plain_i[i] = make_negacyclic_table<ModI>(q[i], c->logN_enc);
-      qm[i] = c->plain_i[i].mod;
-    }
-    for (int j = 0; j < K; j++) {
-      c->coeff_i[j] = make_negacyclic_table<ModI>(Q[j], c->logN_enc);
-      Qm[j] = c->coeff_i[j].mod;
-    }
-    RS_HIP(hipMalloc(&c->d_qmod_i, sizeof(ModI) * L));
-    RS_HIP(hipMemcpy(c->d_qmod_i, qm.data(), sizeof(ModI) * L, hipMemcpyHostToDevice));
-    RS_HIP(hipMalloc(&c->d_Qmod_i, sizeof(ModI) * K));
-    RS_HIP(hipMemcpy(c->d_Qmod_i, Qm.data(), sizeof(ModI) * K, hipMemcpyHostToDevice));
+  const int logn = c->logN_enc;
+  if (!c->use_int) {
+    build_tables<Mod>(q, L, logn, c->plain, &c->d_plain_tabs, &c->d_qmod);
+    build_tables<Mod>(Q, K, logn, c->coeff, &c->d_coeff_tabs, &c->d_Qmod);
+  } else {
+    build_tables<ModI>(q, L, logn, c->plain_i, &c->d_plain_tabs_i, &c->d_qmod_i);
+    build_tables<ModI>(Q, K, logn, c->coeff_i, &c->d_coeff_tabs_i, &c->d_Qmod_i);
     // Hybrid: only ring primes are beyond 2^50 (the 54-bit BFVDefault(2048) prime of bench_logistic_regression_inference.cpp
     // :20-27 under 48/49-bit data primes): the inner products -- everything mod Q_j -- keep the FP64 kernels (msm.hip)
     bool small_Q = !g_tune.force_int_arith;
     for (int j = 0; j < K; j++) small_Q = small_Q && Q[j] < (1ull << 50);
     for (int i = 0; i < L; i++) small_Q = small_Q && q[i] < (1ull << 54);
     c->hybrid = small_Q;
-    if (c->hybrid)
-      for (int j = 0; j < K; j++) c->coeff[j] = make_negacyclic_table<Mod>(Q[j], c->logN_enc);
-  } else {
-    std::vector<Mod> qm(L), Qm(K);
-    for (int i = 0; i < L; i++) {
-      c->plain[i] = make_negacyclic_table<Mod>(q[i], c->logN_enc);
-      qm[i] = c->plain[i].mod;
-    }
-    for (int j = 0; j < K; j++) {
-      c->coeff[j] = make_negacyclic_table<Mod>(Q[j], c->logN_enc);
-      Qm[j] = c->coeff[j].mod;
-    }
-    RS_HIP(hipMalloc(&c->d_qmod, sizeof(Mod) * L));
-    RS_HIP(hipMemcpy(c->d_qmod, qm.data(), sizeof(Mod) * L, hipMemcpyHostToDevice));
-    RS_HIP(hipMalloc(&c->d_Qmod, sizeof(Mod) * K));
-    RS_HIP(hipMemcpy(c->d_Qmod, Qm.data(), sizeof(Mod) * K, hipMemcpyHostToDevice));
+    if (c->hybrid) build_tables<Mod>(Q, K, logn, c->coeff, &c->d_coeff_tabs, nullptr);
   }
+  c->d_qint = upload(c->q, (size_t)L);
+  c->d_Qint = upload(c->Q, (size_t)K);
   // BatchEncoder slot map (SEAL batchencoder.cpp populate_matrix_reps_index_map): generator 3
   // of Z_{2n}^*, row 0 = powers 3^i, row 1 = their negatives, bit-reversed positions.
   {
@@ -733,9 +740,9 @@ int rs_ctx_create(int device, int N, int L, const uint64_t *q, int N_enc, int K,
       map[row | i] = host::bitrev((uint32_t)((mm - pos - 1) >> 1), c->logN_enc);
       pos = (pos * 3) & (mm - 1);
     }
-    RS_HIP(hipMalloc(&c->d_index_map, sizeof(uint32_t) * N_enc));
-    RS_HIP(hipMemcpy(c->d_index_map, map.data(), sizeof(uint32_t) * N_enc, hipMemcpyHostToDevice));
+    c->d_index_map = upload(map.data(), (size_t)N_enc);
   }
+  holder.p = nullptr;
   *out = c;
   RS_API_END
 }
@@ -745,14 +752,25 @@ void rs_ctx_destroy(rs_ctx *c) {
   int prev_device = -1;
   (void)hipGetDevice(&prev_device);
   (void)hipSetDevice(c->device);
-  rs_witness_plans_destroy(c);
-  rs::msm_scratch_release(c);
+  rs::witness_plans_destroy(c);
   for (int i = 0; i < c->L; i++) free_table(c->plain[i]), free_table(c->plain_i[i]);
   for (int j = 0; j < c->K; j++) free_table(c->coeff[j]), free_table(c->coeff_i[j]);
   if (c->d_qmod) (void)hipFree(c->d_qmod);
   if (c->d_Qmod) (void)hipFree(c->d_Qmod);
   if (c->d_qmod_i) (void)hipFree(c->d_qmod_i);
   if (c->d_Qmod_i) (void)hipFree(c->d_Qmod_i);
+  if (c->d_plain_tabs) (void)hipFree(c->d_plain_tabs);
+  if (c->d_coeff_tabs) (void)hipFree(c->d_coeff_tabs);
+  if (c->d_plain_tabs_i) (void)hipFree(c->d_plain_tabs_i);
+  if (c->d_coeff_tabs_i) (void)hipFree(c->d_coeff_tabs_i);
+  if (c->d_qint) (void)hipFree(c->d_qint);
+  if (c->d_Qint) (void)hipFree(c->d_Qint);
+  if (c->msm.d_ones_plain) (void)hipFree(c->msm.d_ones_plain);
+  if (c->msm.copy_stream) (void)hipStreamDestroy(c->msm.copy_stream);
+  for (int b = 0; b < 2; b++) {
+    if (c->msm.ev_copied[b]) (void)hipEventDestroy(c->msm.ev_copied[b]);
+    if (c->msm.ev_freed[b]) (void)hipEventDestroy(c->msm.ev_freed[b]);
+  }
   if (c->d_index_map) (void)hipFree(c->d_index_map);
   if (c->d_noise_thr) (void)hipFree(c->d_noise_thr);
   if (c->d_crt_limbs) (void)hipFree(c->d_crt_limbs);
@@ -859,18 +877,15 @@ int rs_ring_inv(rs_ctx *ctx, uint64_t *d_dst, const uint64_t *d_a, size_t count,
   const size_t words = count * ctx->ring_words();
   if (words) {
     WsScope ws_scope(ctx, S(stream));
-    char *ws = (char *)ws_get(ctx, 7, 256);
-    unsigned *flags = (unsigned *)ws;
-    uint64_t *qint = (uint64_t *)(ws + 64);
+    unsigned *flags = (unsigned *)ws_get(ctx, WS_SMALL, 256);
     RS_HIP(hipMemsetAsync(flags, 0, 4, S(stream)));
-    RS_HIP(hipMemcpyAsync(qint, ctx->q, sizeof(uint64_t) * ctx->L, hipMemcpyHostToDevice, S(stream)));
     const unsigned blocks = (unsigned)std::min<size_t>((words + 255) / 256, 256 * 16);
     if (ctx->use_int)
       hipLaunchKernelGGL(ring_inv_kernel_int, dim3(blocks), dim3(256), 0, S(stream), d_dst, d_a, words, ctx->N, ctx->L,
                          ctx->d_qmod_i, flags);
     else
       hipLaunchKernelGGL(ring_inv_kernel, dim3(blocks), dim3(256), 0, S(stream), d_dst, d_a, words, ctx->N, ctx->L,
-                         ctx->d_qmod, qint, flags);
+                         ctx->d_qmod, ctx->d_qint, flags);
     unsigned h = 0;
     RS_HIP(hipMemcpyAsync(&h, flags, 4, hipMemcpyDeviceToHost, S(stream)));
     RS_HIP(hipStreamSynchronize(S(stream)));
@@ -884,7 +899,7 @@ int rs_ring_is_zero(rs_ctx *ctx, const uint64_t *d_a, size_t count, uint8_t *h_f
   RS_REQUIRE(ctx && d_a && h_flags, "null argument");
   if (count) {
     WsScope ws_scope(ctx, S(stream));
-    unsigned *flags = (unsigned *)ws_get(ctx, 7, std::max<size_t>(256, count * 4));
+    unsigned *flags = (unsigned *)ws_get(ctx, WS_SMALL, std::max<size_t>(256, count * 4));
     RS_HIP(hipMemsetAsync(flags, 0, count * 4, S(stream)));
     hipLaunchKernelGGL(ring_nonzero_kernel, dim3((unsigned)count), dim3(256), 0, S(stream), d_a, ctx->ring_words(), flags);
     std::vector<unsigned> h(count);

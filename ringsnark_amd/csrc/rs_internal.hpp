@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -129,6 +130,45 @@ struct ProfRec {
 struct WitnessPlan;  // witness_plan.hpp
 struct R1cs;         // r1cs in CSR on device
 
+// The workspace slots of a context (rs_ctx::ws, ws_get below), named by what they hold.  Per slot: the functions that
+// take it, its content, and -- where several take it -- why their uses never overlap inside one WsScope.  Entry points
+// never nest a WsScope (rs_ctx::mu is not recursive), so uses in different entry points cannot overlap at all.
+enum WsSlot {
+  WS_MSM_ROWS,       // msm_run: plaintext rows of a term tile, [groups][tile][L][N_enc] lifted words
+  WS_MSM_PARTIAL,    // msm_run: per-chunk partial accumulator sets, [chunks][sets] encoding elements
+  WS_MSM_USED,       // msm_run: one "term was used" word per term of every vector (h_used)
+  WS_MSM_KINDS,      // msm_run: the callers' h_kinds bytes
+  WS_SIDE,           // witness_run: interpolated constant parts [3][L][M]; rs_enc_mul_ring: one encoding element (the product before it is copied back).  Two entry points; the msm_run that rs_enc_mul_ring calls does not take it.
+  WS_COLUMNS,        // witness_chunk, interpolate_arith: the column-major vectors of a chunk, [vectors][columns][M].  Two entry points.
+  WS_BC_SPECTRA,     // bc_h, bc2_h: spectra of the second operand's blocks, [columns][2M | 4M].  A plan is either bc or bc2.
+  WS_SMALL,          // rs_ring_inv, rs_ring_is_zero, normalised_len (poly.hip), rs_r1cs_check, io_eval_run: flag / report words (io_eval_run: + the constants c_j from byte 256);
+                     // msm_run with a host-resident key: the two staging buffers of the key tiles.  vk_create calls rs_ring_inv and then io_eval_at: two scopes, one after the
+                     // other.  normalised_len synchronises before it returns, so its three calls in one scope each take a dead pointer's place.  The provers reach msm_run
+                     // after witness_run, which does not take this slot, and nothing else in a prover's scope does.
+  WS_PROVER_VECS,    // rs_groth16_prove_kinds, rs_rinocchio_prove_kinds: the witness map's output vectors, [4m+1 | 5m+1] ring elements.  Two entry points.
+  WS_NOISE_BITS,     // decode_impl: significant bits of the noise per (element, limb)
+  WS_RINOCCHIO_OUT,  // rs_rinocchio_prove_kinds: the ten inner products and one temporary, [11] encoding elements
+  WS_PASS_A,         // launch_interp (W), launch_h (W1), bc_interp / bc_h (Xhat), bc2_interp / bc2_h (Wy), io_eval_run (tile products P): the first transform workspace.
+                     // launch_interp has enqueued every reader of W when it returns and launch_h of the same witness_chunk takes the slot afresh (ws_get orders a
+                     // reallocation after the stream's work); the bc / bc2 functions are what launch_interp and launch_h call INSTEAD of taking the slot themselves;
+                     // io_eval_run is reached from its own entry points only.
+  WS_PASS_B,         // launch_h (W2), bc_interp / bc_h (Wc), bc2_interp / bc2_h (Ws), io_eval_run (tile prefixes O): the second transform workspace; as WS_PASS_A
+  WS_STAGE_ROWS,     // msm_run: the ring element (1, .., 1) on the call that builds MsmState::d_ones_plain, OR slot-constant values broadcast to ring elements (never both:
+                     // sc_native decides; batch_encode_run takes no workspace); decode_impl: decrypted polynomials [count][L][K][N_enc] between its two kernels.
+                     // The verifiers call rs_enc_decode in a scope of its own, the provers never decode.
+  WS_BC_PRODUCTS,    // bc_h, bc2_h: the block products before the H patch, [columns][2M].  A plan is either bc or bc2.
+  WS_COUNT
+};
+
+// What msm_run (msm.hip) keeps between calls.  Touched by msm_run alone, and every caller of msm_run holds the
+// context's WsScope: no lock of its own.
+struct MsmState {
+  uint64_t *d_ones_plain = nullptr;  // [L][N_enc]: batch encoding of the ring element (1, ..., 1), built at first use (slot-constant vectors)
+  // host-resident keys: copy stream and the events of the two staging buffers (copied: data landed; freed: its readers ran)
+  hipStream_t copy_stream = nullptr;
+  hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_freed[2] = {nullptr, nullptr};
+};
+
 }  // namespace rs
 
 struct rs_r1cs {
@@ -173,11 +213,16 @@ struct rs_ctx {
   rs::NttTable plain[RS_MAX_L];  // mod q_i, length N_enc
   rs::NttTable coeff[RS_MAX_K];  // mod Q_j, length N_enc
   rs::NttTableI plain_i[RS_MAX_L], coeff_i[RS_MAX_K];
+  // device copies of the populated descriptor arrays above ([L], [K]; a hybrid context has both coeff arrays), for the
+  // kernels that pick their table by limb / prime themselves.  Built by rs_ctx_create like everything down to d_Qint.
+  rs::NttTable *d_plain_tabs = nullptr, *d_coeff_tabs = nullptr;
+  rs::NttTableI *d_plain_tabs_i = nullptr, *d_coeff_tabs_i = nullptr;
   rs::ModI *d_qmod_i = nullptr, *d_Qmod_i = nullptr;
   uint32_t *d_index_map = nullptr;  // BatchEncoder slot map, first N entries used
   // constant device arrays of per-limb / per-prime moduli for pointwise kernels
   rs::Mod *d_qmod = nullptr;  // [L]
   rs::Mod *d_Qmod = nullptr;  // [K]
+  uint64_t *d_qint = nullptr, *d_Qint = nullptr;  // q[L], Q[K] as plain integers
   // decode / noise guard (encoding.hip): constants of the (context) built at the first rs_enc_decode / rs_enc_noise_budget and
   // kept -- the digit table of 2^b - 1 for every b < bit_count(Q) in the context's arithmetic, the per-limb CRT constants
   void *d_noise_thr = nullptr;
@@ -186,9 +231,10 @@ struct rs_ctx {
   std::mutex mu;
   std::map<std::pair<size_t, uint64_t>, rs::WitnessPlan *> plans;  // keyed by (m, plan_knob_sig()), witness_plan.hip get_plan
   // workspace cache (grown on demand, per context; calls that need workspace serialise on mu)
-  rs::DeviceBuf ws[16];
+  rs::DeviceBuf ws[rs::WS_COUNT];
   hipStream_t cur_stream = nullptr;  // stream of the call that holds mu (rs::WsScope)
   uint32_t ws_touched = 0;           // workspace slots used by that call
+  rs::MsmState msm;
   bool profiling = false;
   rs_timings timings{};
   std::vector<rs::ProfRec> prof;        // launches recorded since the last rs_profile_read
@@ -210,6 +256,8 @@ struct CtxArith<Mod> {
   static const Table *coeff(const rs_ctx *c) { return c->coeff; }
   static const Mod *qmod(const rs_ctx *c) { return c->d_qmod; }
   static const Mod *Qmod(const rs_ctx *c) { return c->d_Qmod; }
+  static const Table *d_plain(const rs_ctx *c) { return c->d_plain_tabs; }
+  static const Table *d_coeff(const rs_ctx *c) { return c->d_coeff_tabs; }
 };
 template <>
 struct CtxArith<ModI> {
@@ -219,6 +267,8 @@ struct CtxArith<ModI> {
   static const Table *coeff(const rs_ctx *c) { return c->coeff_i; }
   static const ModI *qmod(const rs_ctx *c) { return c->d_qmod_i; }
   static const ModI *Qmod(const rs_ctx *c) { return c->d_Qmod_i; }
+  static const Table *d_plain(const rs_ctx *c) { return c->d_plain_tabs_i; }
+  static const Table *d_coeff(const rs_ctx *c) { return c->d_coeff_tabs_i; }
 };
 // run `f(Mod{})` or `f(ModI{})` according to the context's arithmetic
 #define RS_DISPATCH_ARITH(ctx, CALL_FP, CALL_INT) \
@@ -229,7 +279,9 @@ struct CtxArith<ModI> {
       CALL_FP;                                    \
     }                                             \
   } while (0)
-void *ws_get(rs_ctx *ctx, int slot, size_t bytes);
+// The context's workspace `slot`, grown to `bytes`.  A slot that grows is freed and allocated again, so a pointer taken
+// from a slot is dead after the next ws_get of the same slot within the same WsScope.
+void *ws_get(rs_ctx *ctx, WsSlot slot, size_t bytes);
 // Holds the context lock for one API call on `st` and, on exit, stamps every workspace buffer the
 // call touched with an event on `st` (see DeviceBuf).  Every entry point that calls ws_get owns one.
 // Also pins the HIP current device of the calling thread to the context's device for the call.
@@ -291,8 +343,48 @@ uint32_t inv_reduce_mask(uint64_t p, int logn, int u0 = 0);
 bool fwd_end_needs_reduce(uint64_t p, int logn);
 inline hipStream_t S(rs_stream s) { return (hipStream_t)s; }
 
-// launch helpers implemented in the .hip files
-void msm_scratch_release(rs_ctx *ctx);  // msm.hip
+// ---- host functions that one unit defines and others call: declared here, and only here
 void launch_ntt(rs_ctx *ctx, const NttTable &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st);
 void launch_ntt_int(rs_ctx *ctx, const NttTableI &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st);
+// msm.hip.  msm_run: the caller holds the context's WsScope
+void msm_run(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
+             int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
+             size_t crs_window, const MsmLin *lin = nullptr, bool crs_on_host = false);
+bool msm_supports_lin(const rs_ctx *ctx);
+void batch_encode_run(rs_ctx *ctx, const uint64_t *d_rings, uint64_t *d_plain, size_t count, hipStream_t st);
+void enc_add_run(rs_ctx *ctx, uint64_t *dst, const uint64_t *x, const uint64_t *y, size_t count, hipStream_t st);
+// witness.hip
+void witness_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_asg, const uint64_t *d1, const uint64_t *d2,
+                 const uint64_t *d3, uint64_t *const outs[7], uint64_t *h_Z, hipStream_t st, int slot0 = 0, int nslots = -1,
+                 bool compact = false, const size_t (*rows)[2] = nullptr);
+bool witness_io_shortcut(const rs_r1cs *cs);
+void r1cs_evaluate_run(rs_ctx *ctx, const rs_r1cs *cs, int which, int mode, const uint64_t *d_asg, uint64_t *d_out,
+                       hipStream_t st);
+// witness_plan.hip
+const uint64_t *witness_Z_rows(rs_ctx *ctx, size_t m);
+void witness_plans_destroy(rs_ctx *ctx);  // every plan of the context (rs_ctx_destroy)
+
+// Constants of the Lagrange basis on the domain {0..m-1} (rs_instance_map_eval, rs_io_eval_at):
+// c_j = 1 / prod_{i != j} (j - i) = (-1)^(m-1-j) / (j! (m-1-j)!) as table constants [L][m]: one inversion per limb
+template <class M>
+void lagrange_constants(const rs_ctx *ctx, size_t m, std::vector<uint64_t> &out) {
+  using T = typename HostArith<M>::T;
+  static_assert(sizeof(T) == sizeof(uint64_t), "constants of both arithmetics travel as 64-bit words");
+  out.resize((size_t)ctx->L * m);
+  std::vector<uint64_t> fact(m), ifact(m);
+  for (int l = 0; l < ctx->L; l++) {
+    const uint64_t q = ctx->q[l];
+    RS_REQUIRE(q > m, "ring prime too small for the evaluation domain");
+    fact[0] = 1;
+    for (size_t j = 1; j < m; j++) fact[j] = host::mulmod(fact[j - 1], (uint64_t)j % q, q);
+    ifact[m - 1] = host::invmod(fact[m - 1], q);
+    for (size_t j = m - 1; j > 0; j--) ifact[j - 1] = host::mulmod(ifact[j], (uint64_t)j % q, q);
+    for (size_t j = 0; j < m; j++) {
+      uint64_t v = host::mulmod(ifact[j], ifact[m - 1 - j], q);
+      if ((m - 1 - j) & 1) v = v ? q - v : 0;
+      const T c = HostArith<M>::konst(v, q);
+      std::memcpy(&out[(size_t)l * m + j], &c, sizeof(T));
+    }
+  }
+}
 }  // namespace rs

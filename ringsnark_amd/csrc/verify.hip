@@ -209,29 +209,6 @@ io_eval_kernel(IoCsr<typename ArithOf<M>::T> cs, const typename ArithOf<M>::T *_
   }
 }
 
-// c_j = 1 / prod_{i != j} (j - i) = (-1)^(m-1-j) / (j! (m-1-j)!) as table constants [L][m]: one inversion per limb
-template <class M>
-static void lagrange_constants(const rs_ctx *ctx, size_t m, std::vector<uint64_t> &out) {
-  using T = typename HostArith<M>::T;
-  static_assert(sizeof(T) == sizeof(uint64_t), "constants of both arithmetics travel as 64-bit words");
-  out.resize((size_t)ctx->L * m);
-  std::vector<uint64_t> fact(m), ifact(m);
-  for (int l = 0; l < ctx->L; l++) {
-    const uint64_t q = ctx->q[l];
-    RS_REQUIRE(q > m, "ring prime too small for the evaluation domain");
-    fact[0] = 1;
-    for (size_t j = 1; j < m; j++) fact[j] = host::mulmod(fact[j - 1], (uint64_t)j % q, q);
-    ifact[m - 1] = host::invmod(fact[m - 1], q);
-    for (size_t j = m - 1; j > 0; j--) ifact[j - 1] = host::mulmod(ifact[j], (uint64_t)j % q, q);
-    for (size_t j = 0; j < m; j++) {
-      uint64_t v = host::mulmod(ifact[j], ifact[m - 1 - j], q);
-      if ((m - 1 - j) & 1) v = v ? q - v : 0;
-      const T c = HostArith<M>::konst(v, q);
-      std::memcpy(&out[(size_t)l * m + j], &c, sizeof(T));
-    }
-  }
-}
-
 template <class M>
 static void io_eval_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uint64_t *const outs[3], uint64_t *d_Zt, hipStream_t st) {
   using T = typename ArithOf<M>::T;
@@ -240,9 +217,9 @@ static void io_eval_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uin
   RS_REQUIRE(m < 0xFFFFFFFFull && tiles < 65536, "constraint system too large for the evaluation at a point");
   std::vector<uint64_t> hc;
   lagrange_constants<M>(ctx, m, hc);
-  uint64_t *P = (uint64_t *)ws_get(ctx, 12, tiles * S * sizeof(uint64_t));
-  uint64_t *O = (uint64_t *)ws_get(ctx, 13, tiles * S * sizeof(uint64_t));
-  char *small = (char *)ws_get(ctx, 7, 256 + hc.size() * sizeof(uint64_t));
+  uint64_t *P = (uint64_t *)ws_get(ctx, WS_PASS_A, tiles * S * sizeof(uint64_t));
+  uint64_t *O = (uint64_t *)ws_get(ctx, WS_PASS_B, tiles * S * sizeof(uint64_t));
+  char *small = (char *)ws_get(ctx, WS_SMALL, 256 + hc.size() * sizeof(uint64_t));
   unsigned *d_hit = (unsigned *)small;
   T *d_c = (T *)(small + 256);
   const unsigned hit0[2] = {0xFFFFFFFFu, 0u};

@@ -89,7 +89,7 @@ static void launch_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> 
   // the tile kernel also writes level 15's workspace for the right children ([ncols][M], for ALL the columns it covers)
   // when that fits beside everything else (24 GiB; a configs[3] rank is tight)
   const bool tfwd = tree_fwd_stages<M>(P) && ncols * P->M * sizeof(double) <= ((size_t)24 << 30);
-  T *W = (T *)ws_get(ctx, 12, std::max(chunk * 2 * P->M, (tfwd && chunk < ncols && g_tune.witness_tree_once) ? ncols * P->M : 0) * sizeof(double));
+  T *W = (T *)ws_get(ctx, WS_PASS_A, std::max(chunk * 2 * P->M, (tfwd && chunk < ncols && g_tune.witness_tree_once) ? ncols * P->M : 0) * sizeof(double));
   if (chunk < ncols && g_tune.witness_tree_once) {
     // the tiles of the product tree work in place on the columns: ONE launch over all of them between the sub-chunked
     // phases (tile kernels like long launches: 183.5 -> 176 ms per headline proof when every launch covers a whole chunk,
@@ -140,8 +140,8 @@ static void launch_h(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &cp, 
     return;
   }
   const size_t chunk = std::min(S, big_chunk_cols(P));
-  T *W1 = (T *)ws_get(ctx, 12, chunk * 2 * Mlen * sizeof(double));
-  T *W2 = (T *)ws_get(ctx, 13, chunk * 2 * Mlen * sizeof(double));
+  T *W1 = (T *)ws_get(ctx, WS_PASS_A, chunk * 2 * Mlen * sizeof(double));
+  T *W2 = (T *)ws_get(ctx, WS_PASS_B, chunk * 2 * Mlen * sizeof(double));
   for (size_t c0 = 0; c0 < S; c0 += chunk) {
     const size_t nc = std::min(chunk, S - c0);
     if (Cc && g_tune.witness_h_coset && P->limb[cm.limb0].d_cos_z)
@@ -262,7 +262,7 @@ static void witness_chunk(rs_ctx *ctx, const rs_r1cs *cs, WitnessPlan *P, const 
   for (int o = 0; o < 10; o++)
     if (needed(order[o])) slot_of[order[o]] = nvec++;
   const size_t vec = C * M;
-  T *colbuf = (T *)ws_get(ctx, 5, std::max<size_t>(1, (size_t)nvec * vec) * sizeof(T));
+  T *colbuf = (T *)ws_get(ctx, WS_COLUMNS, std::max<size_t>(1, (size_t)nvec * vec) * sizeof(T));
   auto colv = [&](int k) { return colbuf + (size_t)slot_of[k] * vec; };
   RS_REQUIRE((C % 2) == 0 && (M % 2) == 0, "column tiles move slot pairs and row pairs");
   const dim3 tgrid((unsigned)((C + 63) / 64), (unsigned)((M + 63) / 64));    // transposing kernels: 64 x 64 tiles
@@ -384,7 +384,7 @@ static void witness_run_arith(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_
     for (int w = 0; w < 3; w++)
       for (int i = 0; i < L; i++)
         for (size_t r = 0; r < m; r++) hc[((size_t)w * L + i) * M + r] = HostArith<M_>::plain(cs->h_const[w][(size_t)i * m + r], ctx->q[i]);
-    d_const = (T *)ws_get(ctx, 4, hc.size() * sizeof(T));
+    d_const = (T *)ws_get(ctx, WS_SIDE, hc.size() * sizeof(T));
     RS_HIP(hipMemcpyAsync(d_const, hc.data(), hc.size() * sizeof(T), hipMemcpyHostToDevice, st));
     RS_HIP(hipStreamSynchronize(st));  // hc goes out of scope
     launch_interp<M_>(ctx, P, make_colplans<M_>(ctx, P), d_const, (size_t)3 * L, (size_t)L, 1, 0, st);
@@ -420,8 +420,8 @@ static void witness_run_arith(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_
   }
 }
 void witness_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_asg, const uint64_t *d1, const uint64_t *d2,
-                 const uint64_t *d3, uint64_t *const outs[7], uint64_t *h_Z, hipStream_t st, int slot0 = 0, int nslots = -1,
-                 bool compact = false, const size_t (*rows)[2] = nullptr) {
+                 const uint64_t *d3, uint64_t *const outs[7], uint64_t *h_Z, hipStream_t st, int slot0, int nslots, bool compact,
+                 const size_t (*rows)[2]) {
   RS_DISPATCH_ARITH(ctx, (witness_run_arith<Mod>(ctx, cs, d_asg, d1, d2, d3, outs, h_Z, st, slot0, nslots, compact, rows)),
                     (witness_run_arith<ModI>(ctx, cs, d_asg, d1, d2, d3, outs, h_Z, st, slot0, nslots, compact, rows)));
 }
@@ -432,7 +432,7 @@ static void interpolate_arith(rs_ctx *ctx, const uint64_t *d_y, uint64_t *d_out,
   WitnessPlan *P = get_plan(ctx, n);
   const ColPlansT<M_> cp = make_colplans<M_>(ctx, P);
   const size_t M = P->M, S_ = ctx->ring_words();
-  T *colbuf = (T *)ws_get(ctx, 5, S_ * M * sizeof(T));
+  T *colbuf = (T *)ws_get(ctx, WS_COLUMNS, S_ * M * sizeof(T));
   const dim3 tgrid((unsigned)((S_ + 31) / 32), (unsigned)((M + 31) / 32));
   const ColMap cm{0, ctx->N, 0, ctx->N, ctx->L, ctx->N, 0};
   hipLaunchKernelGGL(transpose_in_kernel<T>, tgrid, dim3(256), 0, st, d_y, colbuf, n, S_, M);

@@ -13,7 +13,6 @@ struct TabPtrs;  // witness_multipass.hpp
 uint64_t konst_word(const rs_ctx *ctx, uint64_t v, uint64_t p);
 bool single_tile_ok(int logM);
 WitnessPlan *get_plan(rs_ctx *ctx, size_t m);
-const uint64_t *witness_Z_rows(rs_ctx *ctx, size_t m);
 template <class M>
 ColPlansT<M> make_colplans(rs_ctx *ctx, const WitnessPlan *P, int limb0 = 0);
 

@@ -239,8 +239,8 @@ void bc_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &cp, typena
   using T = typename ArithOf<M>::T;
   const int logM = P->logM, bc = P->bcLog;
   const size_t Mlen = P->M, B = (size_t)1 << (bc - 1);
-  T *Xhat = (T *)ws_get(ctx, 12, ncols * 2 * Mlen * sizeof(T));
-  T *Wc = (T *)ws_get(ctx, 13, ncols * 2 * Mlen * sizeof(T));
+  T *Xhat = (T *)ws_get(ctx, WS_PASS_A, ncols * 2 * Mlen * sizeof(T));
+  T *Wc = (T *)ws_get(ctx, WS_PASS_B, ncols * 2 * Mlen * sizeof(T));
   BcArgs a{};
   a.src = X;
   a.dst = X;
@@ -288,10 +288,10 @@ void bc_h(rs_ctx *ctx, const WitnessPlan *P, const ColPlansT<M> &cp, const typen
   using CPS = ColPlansT<M>;
   const int logM = P->logM, bc = P->bcLog;
   const size_t Mlen = P->M, B = (size_t)1 << (bc - 1), B2 = 2 * B, nb = Mlen / B;
-  T *Xhat = (T *)ws_get(ctx, 12, ncols * 2 * Mlen * sizeof(T));
-  T *Wc = (T *)ws_get(ctx, 13, ncols * 4 * Mlen * sizeof(T));
-  T *Yhat = (T *)ws_get(ctx, 6, ncols * 2 * Mlen * sizeof(T));
-  T *Pbuf = (T *)ws_get(ctx, 15, ncols * 2 * Mlen * sizeof(T));
+  T *Xhat = (T *)ws_get(ctx, WS_PASS_A, ncols * 2 * Mlen * sizeof(T));
+  T *Wc = (T *)ws_get(ctx, WS_PASS_B, ncols * 4 * Mlen * sizeof(T));
+  T *Yhat = (T *)ws_get(ctx, WS_BC_SPECTRA, ncols * 2 * Mlen * sizeof(T));
+  T *Pbuf = (T *)ws_get(ctx, WS_BC_PRODUCTS, ncols * 2 * Mlen * sizeof(T));
   BcArgs a{};
   a.bcLog = bc;
   a.logM = logM;
@@ -408,8 +408,8 @@ void bc2_interp(rs_ctx *ctx, const WitnessPlan *P, const ColPlans &cp, double *X
   a.src = X;
   a.dst = X;
   if (phases & 5) {  // the tree tiles work in place: no workspace (and `ncols` may then be a whole chunk)
-    a.Wy = (double *)ws_get(ctx, 12, ncols * 2 * Mlen * sizeof(double));
-    a.Ws = (double *)ws_get(ctx, 13, ncols * 4 * Mlen * sizeof(double));
+    a.Wy = (double *)ws_get(ctx, WS_PASS_A, ncols * 2 * Mlen * sizeof(double));
+    a.Ws = (double *)ws_get(ctx, WS_PASS_B, ncols * 4 * Mlen * sizeof(double));
   }
   a.logM = logM;
   a.m = (int)P->m;
@@ -466,10 +466,10 @@ void bc2_h(rs_ctx *ctx, const WitnessPlan *P, const ColPlans &cp, const double *
                   hipStream_t st) {
   const int logM = P->logM, logY = logM + 1 - BC2_LOGB;
   const size_t Mlen = P->M;
-  double *Wy = (double *)ws_get(ctx, 12, ncols * 2 * Mlen * sizeof(double));
-  double *Ws = (double *)ws_get(ctx, 13, ncols * 4 * Mlen * sizeof(double));
-  double *WsA = (double *)ws_get(ctx, 6, ncols * 4 * Mlen * sizeof(double));
-  double *Pbuf = (double *)ws_get(ctx, 15, ncols * 2 * Mlen * sizeof(double));
+  double *Wy = (double *)ws_get(ctx, WS_PASS_A, ncols * 2 * Mlen * sizeof(double));
+  double *Ws = (double *)ws_get(ctx, WS_PASS_B, ncols * 4 * Mlen * sizeof(double));
+  double *WsA = (double *)ws_get(ctx, WS_BC_SPECTRA, ncols * 4 * Mlen * sizeof(double));
+  double *Pbuf = (double *)ws_get(ctx, WS_BC_PRODUCTS, ncols * 2 * Mlen * sizeof(double));
   Bc2Args a{};
   a.logM = logM;
   a.m = (int)P->m;

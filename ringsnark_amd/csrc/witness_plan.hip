@@ -517,7 +517,7 @@ static uint64_t plan_knob_sig() {
     h = (h ^ (uint64_t)(uint32_t)v) * 1099511628211ull;
   return h;
 }
-// Plans are cached per (m, plan_knob_sig()) and live until rs_witness_plans_destroy: a plan is never freed under a call
+// Plans are cached per (m, plan_knob_sig()) and live until witness_plans_destroy: a plan is never freed under a call
 // that holds its tables, and no lookup synchronises.  Cost: a context on which plan-shaping knobs are flipped (tests and
 // tools/ only; the product never changes a knob) keeps one plan per distinct signature it has seen.
 WitnessPlan *get_plan(rs_ctx *ctx, size_t m) {
@@ -595,11 +595,9 @@ bool single_tile_ok(int logM) {
   return logM <= g_tune.witness_lds_logM || (logM == 14 && g_tune.witness_lds_logM == 13);
 }
 
-}  // namespace rs
-
-using namespace rs;
-
-extern "C" void rs_witness_plans_destroy(rs_ctx *ctx) {
+void witness_plans_destroy(rs_ctx *ctx) {
   for (auto &kv : ctx->plans) free_plan(kv.second);
   ctx->plans.clear();
 }
+
+}  // namespace rs

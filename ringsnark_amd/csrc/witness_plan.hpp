@@ -54,5 +54,3 @@ struct WitnessPlan {
 };
 
 }  // namespace rs
-
-extern "C" void rs_witness_plans_destroy(rs_ctx *ctx);  // every plan of the context (rs_ctx_destroy)
