@@ -61,6 +61,16 @@ class VerifyReport(C.Structure):
                 ("first_limb", C.c_uint32), ("first_slot", C.c_uint32), ("lhs", C.c_uint64), ("rhs", C.c_uint64)]
 
 
+class Groth16KeyOut(C.Structure):
+    _fields_ = [("s_pows", vp), ("delta_ts", vp), ("delta_mid", vp), ("d_alpha", vp), ("d_beta", vp), ("host_key", C.c_int),
+                ("tile", C.c_size_t)]
+
+
+class RinocchioKeyOut(C.Structure):
+    _fields_ = [("s_pows", vp), ("alpha_s_pows", vp), ("beta_prods", vp), ("d_beta_rv_ts", vp), ("d_beta_rw_ts", vp),
+                ("d_beta_ry_ts", vp), ("host_key", C.c_int), ("tile", C.c_size_t)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int), ("total_ms", C.c_float), ("alg_bytes", C.c_double),
                 ("fp64_ops", C.c_double)]
@@ -151,6 +161,12 @@ VERIFY_SIGNATURES = {  # every function of include/ringsnark_amd/verify.h
     "rs_rinocchio_verify": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(VerifyReport), vp]),
 }
 
+KEYGEN_SIGNATURES = {  # every function of include/ringsnark_amd/keygen.h
+    "rs_groth16_keygen": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, u64p, C.POINTER(Groth16KeyOut), vp]),
+    "rs_rinocchio_keygen": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64p, C.POINTER(RinocchioKeyOut), vp]),
+    "rs_enc_encode_linear": (C.c_int, [vp, vp, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t, C.c_uint64, vp, vp]),
+}
+
 _lib = None
 
 
@@ -164,7 +180,7 @@ def load():
             "ringsnark_amd/librs_hip.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
             "the HIP library is the only implementation, there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **VERIFY_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **VERIFY_SIGNATURES, **KEYGEN_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

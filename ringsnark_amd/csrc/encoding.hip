@@ -133,13 +133,6 @@ crt_decode_kernel(const double *__restrict__ V, uint64_t *__restrict__ rings, in
 }
 
 // ---- encode ----------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t splitmix_at(uint64_t seed, uint64_t k) {  // k-th output (1-based) of the stream
-  uint64_t z = seed + k * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 // One workgroup per (element, limb, prime j): c1 = a, c0 = -(a*s + t*e) + NTT(lift(BatchEncode(ring limb))).
 // Stream layout of oracle/rs_oracle.c rso_encrypt_symmetric: draws 1..n are the ternary error,
 // draw n + j*n + x + 1 is a_j[x].  grid (count * L, K); PER = n / blockDim <= 16
@@ -335,8 +328,6 @@ encode_kernel_int(const uint64_t *__restrict__ rings, const uint64_t *__restrict
     }
   }
 }
-
-static int enc_threads(int logn) { return (int)std::max(64, std::min(1024, (1 << logn) / 8)); }
 
 // Host side of the noise guard: bit_count(Q) and the mixed-radix digits (radices Q_0, Q_1, ...) of 2^b - 1 for every
 // b < bit_count(Q), by exact multi-word arithmetic (K <= 12 words of 62 bits).
@@ -792,26 +783,32 @@ lagrange_kernel_int(const uint64_t *__restrict__ s, uint64_t *__restrict__ Ht, u
 }
 }  // namespace rs
 
-extern "C" {
-
-int rs_instance_map_eval(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uint64_t *d_At, uint64_t *d_Bt, uint64_t *d_Ct,
-                         uint64_t *d_Ht, uint64_t *d_Zt, rs_stream stream) {
-  RS_API_BEGIN_CTX(ctx)
-  RS_REQUIRE(ctx && cs && d_s && d_At && d_Bt && d_Ct && d_Ht && d_Zt, "null argument");
+namespace rs {
+void instance_map_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uint64_t *d_At, uint64_t *d_Bt, uint64_t *d_Ct,
+                      uint64_t *d_Ht, uint64_t *d_Zt, hipStream_t st, bool wipe) {
   const size_t m = cs->m, SW = ctx->ring_words();
   const int L = ctx->L;
-  hipStream_t st = S(stream);
   uint64_t *D = nullptr;
   RS_HIP(hipMalloc(&D, m * SW * sizeof(uint64_t)));
   struct Guard {
     std::vector<void *> p;
     rs_r1cs *tr = nullptr;
+    void *wipe_p = nullptr;  // overwritten with zeros before the release (nothing enqueued may still use it: the stream is drained first)
+    size_t wipe_bytes = 0;
+    hipStream_t st = nullptr;
     ~Guard() {
+      if (wipe_p) {
+        (void)hipStreamSynchronize(st);
+        (void)hipMemset(wipe_p, 0, wipe_bytes);
+        (void)hipDeviceSynchronize();
+      }
       for (void *x : p) (void)hipFree(x);
       if (tr) rs_r1cs_destroy(tr);
     }
   } guard;
   guard.p.push_back(D);
+  guard.st = st;
+  if (wipe) guard.wipe_p = D, guard.wipe_bytes = m * SW * sizeof(uint64_t);
   std::vector<uint64_t> hc;  // slot-constant factors c_j [L][m], table constants of the context's arithmetic
   RS_DISPATCH_ARITH(ctx, lagrange_constants<Mod>(ctx, m, hc), lagrange_constants<ModI>(ctx, m, hc));
   double *d_c = nullptr;
@@ -873,7 +870,18 @@ int rs_instance_map_eval(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, ui
              rs_last_error());
   uint64_t *outs[3] = {d_At, d_Bt, d_Ct};
   for (int w = 0; w < 3; w++) r1cs_evaluate_run(ctx, guard.tr, w, RS_EVAL_FULL, D, outs[w], st);
+  RS_HIP(hipGetLastError());
   RS_HIP(hipStreamSynchronize(st));
+}
+}  // namespace rs
+
+extern "C" {
+
+int rs_instance_map_eval(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uint64_t *d_At, uint64_t *d_Bt, uint64_t *d_Ct,
+                         uint64_t *d_Ht, uint64_t *d_Zt, rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  RS_REQUIRE(ctx && cs && d_s && d_At && d_Bt && d_Ct && d_Ht && d_Zt, "null argument");
+  instance_map_run(ctx, cs, d_s, d_At, d_Bt, d_Ct, d_Ht, d_Zt, S(stream), false);
   RS_API_END
 }
 

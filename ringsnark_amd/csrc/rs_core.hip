@@ -672,7 +672,7 @@ using namespace rs;
 extern "C" {
 
 const char *rs_last_error(void) { return g_last_error.c_str(); }
-int rs_version(void) { return 103; }  // 103: verify.h (rs_io_eval_at, verifiers); 102: rs_r1cs_check; 101: rs_msm_vec::slot_const (struct must be zero-initialised), rs_enc_noise_budget, RS_ERR_NOISE
+int rs_version(void) { return 104; }  // 104: keygen.h (generators); 103: verify.h (rs_io_eval_at, verifiers); 102: rs_r1cs_check; 101: rs_msm_vec::slot_const (struct must be zero-initialised), rs_enc_noise_budget, RS_ERR_NOISE
 
 int rs_ctx_create(int device, int N, int L, const uint64_t *q, int N_enc, int K, const uint64_t *Q, rs_ctx **out) {
   RS_API_BEGIN
@@ -770,6 +770,11 @@ void rs_ctx_destroy(rs_ctx *c) {
   for (int b = 0; b < 2; b++) {
     if (c->msm.ev_copied[b]) (void)hipEventDestroy(c->msm.ev_copied[b]);
     if (c->msm.ev_freed[b]) (void)hipEventDestroy(c->msm.ev_freed[b]);
+  }
+  if (c->keygen.copy_stream) (void)hipStreamDestroy(c->keygen.copy_stream);
+  for (int b = 0; b < 2; b++) {
+    if (c->keygen.ev_encoded[b]) (void)hipEventDestroy(c->keygen.ev_encoded[b]);
+    if (c->keygen.ev_drained[b]) (void)hipEventDestroy(c->keygen.ev_drained[b]);
   }
   if (c->d_index_map) (void)hipFree(c->d_index_map);
   if (c->d_noise_thr) (void)hipFree(c->d_noise_thr);

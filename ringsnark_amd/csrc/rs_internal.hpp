@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -157,6 +158,7 @@ enum WsSlot {
                      // sc_native decides; batch_encode_run takes no workspace); decode_impl: decrypted polynomials [count][L][K][N_enc] between its two kernels.
                      // The verifiers call rs_enc_decode in a scope of its own, the provers never decode.
   WS_BC_PRODUCTS,    // bc_h, bc2_h: the block products before the H patch, [columns][2M].  A plan is either bc or bc2.
+  WS_KEYGEN_STAGE,   // keygen_run (keygen.hip) with a host-resident key: the two staging buffers of encoded tiles, [2][tile] encoding elements (ciphertexts only, nothing secret)
   WS_COUNT
 };
 
@@ -167,6 +169,13 @@ struct MsmState {
   // host-resident keys: copy stream and the events of the two staging buffers (copied: data landed; freed: its readers ran)
   hipStream_t copy_stream = nullptr;
   hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_freed[2] = {nullptr, nullptr};
+};
+
+// What keygen_run (keygen.hip) keeps between calls for host-resident keys: the copy stream and the events of the two
+// staging buffers (encoded: the kernel of a tile ran; drained: its copy to the host landed).  Touched under the WsScope.
+struct KeygenState {
+  hipStream_t copy_stream = nullptr;
+  hipEvent_t ev_encoded[2] = {nullptr, nullptr}, ev_drained[2] = {nullptr, nullptr};
 };
 
 }  // namespace rs
@@ -235,6 +244,7 @@ struct rs_ctx {
   hipStream_t cur_stream = nullptr;  // stream of the call that holds mu (rs::WsScope)
   uint32_t ws_touched = 0;           // workspace slots used by that call
   rs::MsmState msm;
+  rs::KeygenState keygen;
   bool profiling = false;
   rs_timings timings{};
   std::vector<rs::ProfRec> prof;        // launches recorded since the last rs_profile_read
@@ -360,6 +370,21 @@ void witness_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_asg, const ui
 bool witness_io_shortcut(const rs_r1cs *cs);
 void r1cs_evaluate_run(rs_ctx *ctx, const rs_r1cs *cs, int which, int mode, const uint64_t *d_asg, uint64_t *d_out,
                        hipStream_t st);
+// encoding.hip.  The body of rs_instance_map_eval (outputs as there, all required).  wipe: the call's scratch -- the
+// Lagrange values u_j(s) -- is overwritten with zeros before it is released (the generators: s is a trapdoor element).
+void instance_map_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uint64_t *d_At, uint64_t *d_Bt, uint64_t *d_Ct,
+                      uint64_t *d_Ht, uint64_t *d_Zt, hipStream_t st, bool wipe);
+// threads of a workgroup that holds one length-2^logn transform in LDS (decode, encode, keygen)
+inline int enc_threads(int logn) { return (int)std::max(64, std::min(1024, (1 << logn) / 8)); }
+#if defined(__HIPCC__)
+// k-th output (1-based) of the splitmix64 stream `seed`: the sampler of rs_enc_encode and the generators (oracle/rs_oracle.c)
+__device__ __forceinline__ uint64_t splitmix_at(uint64_t seed, uint64_t k) {
+  uint64_t z = seed + k * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+#endif
 // witness_plan.hip
 const uint64_t *witness_Z_rows(rs_ctx *ctx, size_t m);
 void witness_plans_destroy(rs_ctx *ctx);  // every plan of the context (rs_ctx_destroy)

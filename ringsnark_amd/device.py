@@ -303,6 +303,70 @@ class Device:
         """rinocchio::verifier (rinocchio.tcc:192-295): proof [9]; failed bit c = check c of verify.h (V', W', Y', H', L_beta, P)."""
         return self._verify(self.lib.rs_rinocchio_verify, vk, "rinocchio", 9, primary, proof, empty)
 
+    # ---- generators (ringsnark_amd/keygen.h)
+    KEYGEN_SEED_STRIDE = 1 << 40  # seeds=<int>: vector v of a key encodes from seed + v * 2^40 (disjoint streams for any length < 2^40)
+
+    def _keygen_seeds(self, seeds, n):
+        """n per-vector seeds in enc_encode's convention (element k of vector v: the oracle's stream seeds[v] * 65537 + k)."""
+        if seeds is None:
+            seeds = 1
+        if isinstance(seeds, int):
+            seeds = [seeds + v * self.KEYGEN_SEED_STRIDE for v in range(n)]
+        assert len(seeds) == n, (len(seeds), n)
+        return (C.c_uint64 * n)(*[(int(x) * 65537) % 2**64 for x in seeds])
+
+    def _key_vector(self, count, host):
+        if host:
+            return self.host_alloc(max(count, 1) * self.enc_words)
+        return self.enc_empty(count)
+
+    def enc_encode_linear(self, sk, rows, seed, coefs=None):
+        """rs_enc_encode_linear: E(sum_r coefs[r] * rows[r][k]) for every k; rows: one to three tensors [count][L][N], coefs:
+        per term a ring element [L][N] or None (= 1).  With one term and no coefficient: the bytes of enc_encode(sk, rows[0], seed)."""
+        n = len(rows)
+        coefs = list(coefs) if coefs is not None else [None] * n
+        count = self._count(rows[0], self.ring_words)
+        assert all(self._count(r, self.ring_words) == count and r.is_contiguous() for r in rows)
+        out = self.enc_empty(count)
+        cp = (C.c_void_p * n)(*[None if c is None else c.data_ptr() for c in coefs])
+        rp = (C.c_void_p * n)(*[r.data_ptr() for r in rows])
+        _lib.check(self.lib.rs_enc_encode_linear(self.h, _ptr(sk), cp, rp, n, count, C.c_uint64((seed * 65537) % 2**64), _ptr(out),
+                                                 self.stream()))
+        return out
+
+    def groth16_keygen(self, dcs, vk, seeds=None, host=False, tile=0):
+        """groth16::generator (groth16.tcc:5-66) on the device: the proving key of the trapdoor `vk` (the dict groth16_vk
+        takes: s, alpha, beta, gamma, delta, sk), as the dict groth16_prove accepts.  seeds: None, one integer, or five
+        (s_pows, delta_ts, delta_mid, alpha, beta) in enc_encode's convention; their ranges must not intersect.
+        host: the three vectors are HostWords (a key larger than HBM), encoded in tiles of `tile` elements."""
+        t = {k: self._vk_part(vk[k]) for k in ("s", "alpha", "beta", "delta", "sk")}
+        self.sync()
+        m, n_aux = dcs.m, dcs.n_vars - dcs.n_inputs
+        pk = dict(s_pows=self._key_vector(m + 1, host), delta_ts=self._key_vector(m + 1, host),
+                  delta_mid=self._key_vector(n_aux, host) if n_aux else None, alpha=self.enc_empty(), beta=self.enc_empty())
+        addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
+        out = _lib.Groth16KeyOut(addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk["delta_mid"]), pk["alpha"].data_ptr(),
+                                 pk["beta"].data_ptr(), 1 if host else 0, tile)
+        _lib.check(self.lib.rs_groth16_keygen(self.h, dcs.h, _ptr(t["s"]), _ptr(t["alpha"]), _ptr(t["beta"]), _ptr(t["delta"]),
+                                              _ptr(t["sk"]), self._keygen_seeds(seeds, 5), C.byref(out), self.stream()))
+        return pk
+
+    def rinocchio_keygen(self, dcs, vk, seeds=None, host=False, tile=0):
+        """rinocchio::generator (rinocchio.tcc:5-72): the dict rinocchio_prove accepts, from the dict rinocchio_vk takes.
+        seeds: s_pows, alpha_s_pows, beta_prods, beta_rv_ts, beta_rw_ts, beta_ry_ts."""
+        t = {k: self._vk_part(vk[k]) for k in ("s", "alpha", "beta", "r_v", "r_w", "r_y", "sk")}
+        self.sync()
+        m, n_aux = dcs.m, dcs.n_vars - dcs.n_inputs
+        pk = dict(s_pows=self._key_vector(m + 1, host), alpha_s_pows=self._key_vector(m + 1, host),
+                  beta_prods=self._key_vector(n_aux, host) if n_aux else None, beta_rv_ts=self.enc_empty(),
+                  beta_rw_ts=self.enc_empty(), beta_ry_ts=self.enc_empty())
+        addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
+        out = _lib.RinocchioKeyOut(addr(pk["s_pows"]), addr(pk["alpha_s_pows"]), addr(pk["beta_prods"]), pk["beta_rv_ts"].data_ptr(),
+                                   pk["beta_rw_ts"].data_ptr(), pk["beta_ry_ts"].data_ptr(), 1 if host else 0, tile)
+        _lib.check(self.lib.rs_rinocchio_keygen(self.h, dcs.h, *[_ptr(t[k]) for k in ("s", "alpha", "beta", "r_v", "r_w", "r_y", "sk")],
+                                                self._keygen_seeds(seeds, 6), C.byref(out), self.stream()))
+        return pk
+
     # ---- 8(f) f4
     def enc_serialize(self, enc, empty=None):
         """Encoding elements (a proof, a key vector) -> bytes in the wire format of ringsnark_amd.h."""
