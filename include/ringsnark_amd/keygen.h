@@ -32,7 +32,9 @@
  * plus, for a host-resident key, two staging buffers of `tile` encoding elements -- computed, not measured: about 80 GiB
  * at 2^16 constraints of the headline shape.  Everything derived from the trapdoor (the Lagrange values, the rows, Z(s),
  * delta^-1 and the coefficient elements) is overwritten with zeros before it is released, as rs_*_vk_destroy does.
- * Both calls synchronise. */
+ * Both calls synchronise.
+ *
+ * Seeded keys -- the vectors stored as their c0 halves and a public seed, half the size -- are in seeded.h (rs_version() >= 105). */
 #ifndef RINGSNARK_AMD_KEYGEN_H
 #define RINGSNARK_AMD_KEYGEN_H
 #include "../ringsnark_amd.h"

@@ -71,6 +71,24 @@ class RinocchioKeyOut(C.Structure):
                 ("d_beta_ry_ts", vp), ("host_key", C.c_int), ("tile", C.c_size_t)]
 
 
+class Groth16SeededKeyOut(Groth16KeyOut):  # rs_groth16_seeded_key_out: the same members, the three vectors compact
+    pass
+
+
+class RinocchioSeededKeyOut(RinocchioKeyOut):
+    pass
+
+
+class Groth16PKSeeded(C.Structure):
+    _fields_ = [("s_pows", vp), ("delta_ts", vp), ("delta_mid", vp), ("pub_seeds", C.c_uint64 * 3), ("d_alpha", vp), ("d_beta", vp),
+                ("window", C.c_size_t), ("host_key", C.c_int)]
+
+
+class RinocchioPKSeeded(C.Structure):
+    _fields_ = [("s_pows", vp), ("alpha_s_pows", vp), ("beta_prods", vp), ("pub_seeds", C.c_uint64 * 3), ("d_beta_rv_ts", vp),
+                ("d_beta_rw_ts", vp), ("d_beta_ry_ts", vp), ("window", C.c_size_t), ("host_key", C.c_int)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int), ("total_ms", C.c_float), ("alg_bytes", C.c_double),
                 ("fp64_ops", C.c_double)]
@@ -167,6 +185,16 @@ KEYGEN_SIGNATURES = {  # every function of include/ringsnark_amd/keygen.h
     "rs_enc_encode_linear": (C.c_int, [vp, vp, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t, C.c_uint64, vp, vp]),
 }
 
+SEEDED_SIGNATURES = {  # every function of include/ringsnark_amd/seeded.h
+    "rs_enc_expand_seeded": (C.c_int, [vp, vp, C.c_uint64, C.c_size_t, C.c_size_t, vp, vp]),
+    "rs_groth16_keygen_seeded": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, u64p, u64p, C.POINTER(Groth16SeededKeyOut), vp]),
+    "rs_rinocchio_keygen_seeded": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64p, u64p, C.POINTER(RinocchioSeededKeyOut), vp]),
+    "rs_msm_seeded": (C.c_int, [vp, C.POINTER(vp), u64p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(MsmVec), C.c_int, C.c_int, vp,
+                                C.POINTER(C.c_size_t), vp]),
+    "rs_groth16_prove_seeded": (C.c_int, [vp, vp, C.POINTER(Groth16PKSeeded), vp, u8p, vp, C.POINTER(C.c_int), vp]),
+    "rs_rinocchio_prove_seeded": (C.c_int, [vp, vp, C.POINTER(RinocchioPKSeeded), vp, u8p, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
+}
+
 _lib = None
 
 
@@ -180,7 +208,8 @@ def load():
             "ringsnark_amd/librs_hip.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
             "the HIP library is the only implementation, there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **VERIFY_SIGNATURES, **KEYGEN_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **VERIFY_SIGNATURES, **KEYGEN_SIGNATURES,
+                              **SEEDED_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

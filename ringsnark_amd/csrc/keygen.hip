@@ -41,9 +41,11 @@ __device__ __forceinline__ uint64_t modulus_u64(const ModI &m) { return m.p; }
 // One workgroup per (element, limb); PER = n / blockDim <= 16.  Stream layout of oracle/rs_oracle.c rso_encrypt_symmetric,
 // as encode_kernel: draws 1..n are the ternary error (shared by the K primes), draw n + j*n + x + 1 is a_j[x].
 // LDS: one tile of n values (128 KiB + padding at n = 16384: one workgroup per CU, no second buffer).
-template <class M>
+// pub0: the seed of the vector's PUBLIC stream, which a is drawn from (seeded.h; pub0 == seed0: the one stream of keygen.h).
+// COMPACT: a seeded vector -- c1 is not stored and the elements are [L][K][n] words apart.
+template <class M, bool COMPACT>
 __global__ void __launch_bounds__(1024)
-keygen_encode_kernel(LinRows lf, const uint64_t *__restrict__ sk, uint64_t *__restrict__ enc, uint64_t seed0, int N, int L, int K,
+keygen_encode_kernel(LinRows lf, const uint64_t *__restrict__ sk, uint64_t *__restrict__ enc, uint64_t seed0, uint64_t pub0, int N, int L, int K,
                      int logn, const uint32_t *__restrict__ index_map,
                      const NttTableT<typename ArithOf<M>::T, M> *__restrict__ plain_tabs,
                      const NttTableT<typename ArithOf<M>::T, M> *__restrict__ coeff_tabs) {
@@ -58,6 +60,7 @@ keygen_encode_kernel(LinRows lf, const uint64_t *__restrict__ sk, uint64_t *__re
   const NttTableT<T, M> pt = plain_tabs[limb];
   const M tmod = pt.mod;
   const uint64_t seed = (seed0 + elem) * 1315423911ull + (uint64_t)limb + 1;  // rso_enc_encode's per-limb stream
+  const uint64_t pseed = (pub0 + elem) * 1315423911ull + (uint64_t)limb + 1;
   // 1. the linear form per slot, scattered (BatchEncoder::encode)
   for (int p = threadIdx.x; p < n; p += blockDim.x) s[pidx(p)] = T(0);
   __syncthreads();
@@ -98,42 +101,47 @@ keygen_encode_kernel(LinRows lf, const uint64_t *__restrict__ sk, uint64_t *__re
     }
     __syncthreads();
     lds_ntt_fwd(s, logn, ct.d_tw, 1, mod, FP ? ct.fwd_red_mask : 0u);
-    uint64_t *c0 = enc + (el * 2 * K + j) * (size_t)n, *c1 = c0 + (size_t)K * n;
+    uint64_t *c0 = enc + (el * (COMPACT ? 1 : 2) * K + j) * (size_t)n, *c1 = c0 + (size_t)K * n;
     const uint64_t *sj = sk + (size_t)j * n;
 #pragma unroll
     for (int k = 0; k < 16; k++) {
       const int p = threadIdx.x + k * blockDim.x;
       if (p < n) {
-        const uint64_t a = splitmix_at(seed, (uint64_t)n + (uint64_t)j * n + (uint64_t)p + 1) % Q;
+        const uint64_t a = splitmix_at(pseed, (uint64_t)n + (uint64_t)j * n + (uint64_t)p + 1) % Q;
         const T as = mulmod_dd(from_res<T>(a), from_res<T>(sj[p]), mod);
-        c1[p] = a;
+        if (!COMPACT) c1[p] = a;
         c0[p] = to_res(canon(subm(reduce(s[pidx(p)], mod), as, mod), mod));
       }
     }
   }
 }
 
-template <class M>
-static void encode_linear_launch(rs_ctx *ctx, const LinRows &lf, const uint64_t *d_sk, size_t count, uint64_t seed, uint64_t *d_enc,
-                                 hipStream_t st) {
+template <class M, bool COMPACT>
+static void encode_linear_launch(rs_ctx *ctx, const LinRows &lf, const uint64_t *d_sk, size_t count, uint64_t seed, uint64_t pub,
+                                 uint64_t *d_enc, hipStream_t st) {
   using T = typename ArithOf<M>::T;
   if (count == 0) return;
   RS_REQUIRE(count * (size_t)ctx->L < ((size_t)1 << 31), "too many elements for one launch");
   const size_t lds = padded_len((size_t)ctx->N_enc) * sizeof(T);
   const int thr = std::max(enc_threads(ctx->logN_enc), ctx->N_enc / 16);  // as rs_enc_encode: at most 16 coefficients per thread
-  set_max_dyn_lds((const void *)keygen_encode_kernel<M>, (int)lds);
+  set_max_dyn_lds((const void *)keygen_encode_kernel<M, COMPACT>, (int)lds);
   const double n = (double)ctx->N_enc, el = (double)count * ctx->L;
   // algorithmic bytes: the rows and the written encodings; transforms: K + 1 per (element, limb)
-  ProfScope p(ctx, st, "keygen_encode", el * 8 * (lf.R * ctx->N + 2.0 * ctx->K * n), el * (ctx->K + 1) * ntt_fp64(n, ctx->logN_enc));
-  hipLaunchKernelGGL(keygen_encode_kernel<M>, dim3((unsigned)(count * ctx->L)), dim3(thr), lds, st, lf, d_sk, d_enc, seed, ctx->N,
+  ProfScope p(ctx, st, "keygen_encode", el * 8 * (lf.R * ctx->N + (COMPACT ? 1.0 : 2.0) * ctx->K * n), el * (ctx->K + 1) * ntt_fp64(n, ctx->logN_enc));
+  hipLaunchKernelGGL((keygen_encode_kernel<M, COMPACT>), dim3((unsigned)(count * ctx->L)), dim3(thr), lds, st, lf, d_sk, d_enc, seed, pub, ctx->N,
                      ctx->L, ctx->K, ctx->logN_enc, ctx->d_index_map, CtxArith<M>::d_plain(ctx), CtxArith<M>::d_coeff(ctx));
   RS_HIP(hipGetLastError());
 }
 
-static void encode_linear(rs_ctx *ctx, const LinRows &lf, const uint64_t *d_sk, size_t count, uint64_t seed, uint64_t *d_enc,
-                          hipStream_t st) {
-  RS_DISPATCH_ARITH(ctx, (encode_linear_launch<Mod>(ctx, lf, d_sk, count, seed, d_enc, st)),
-                    (encode_linear_launch<ModI>(ctx, lf, d_sk, count, seed, d_enc, st)));
+// pub: the seed of the public stream (== seed: keygen.h); compact: the seeded layout, c0 only
+static void encode_linear(rs_ctx *ctx, const LinRows &lf, const uint64_t *d_sk, size_t count, uint64_t seed, uint64_t pub, bool compact,
+                          uint64_t *d_enc, hipStream_t st) {
+  if (compact)
+    RS_DISPATCH_ARITH(ctx, (encode_linear_launch<Mod, true>(ctx, lf, d_sk, count, seed, pub, d_enc, st)),
+                      (encode_linear_launch<ModI, true>(ctx, lf, d_sk, count, seed, pub, d_enc, st)));
+  else
+    RS_DISPATCH_ARITH(ctx, (encode_linear_launch<Mod, false>(ctx, lf, d_sk, count, seed, pub, d_enc, st)),
+                      (encode_linear_launch<ModI, false>(ctx, lf, d_sk, count, seed, pub, d_enc, st)));
 }
 
 constexpr size_t KEYGEN_HOST_TILE = 64;  // elements per staging buffer of a host-resident key when the caller names none
@@ -142,14 +150,15 @@ constexpr size_t KEYGEN_HOST_TILE = 64;  // elements per staging buffer of a hos
 // to_host: dst is a host pointer; tiles go through the two staging buffers, the copy of a tile on the copy stream under
 // the kernel of the next one.  Ordering as msm_run's host-key tiles, the directions reversed: the copy stream waits for
 // ev_encoded[buf] (the kernel filled the buffer), the kernel that refills the buffer waits for ev_drained[buf].
-static void encode_vector(rs_ctx *ctx, LinRows lf, const uint64_t *d_sk, size_t count, uint64_t seed, uint64_t *dst, bool to_host,
-                          size_t tile, uint64_t *stage, hipStream_t st) {
+// pub, compact: as encode_linear; the tiles and copies of a compact vector are half the size.
+static void encode_vector(rs_ctx *ctx, LinRows lf, const uint64_t *d_sk, size_t count, uint64_t seed, uint64_t pub, bool compact,
+                          uint64_t *dst, bool to_host, size_t tile, uint64_t *stage, hipStream_t st) {
   if (!to_host) {
-    encode_linear(ctx, lf, d_sk, count, seed, dst, st);
+    encode_linear(ctx, lf, d_sk, count, seed, pub, compact, dst, st);
     return;
   }
   KeygenState &kg = ctx->keygen;
-  const size_t S = ctx->ring_words(), EW = ctx->enc_words();
+  const size_t S = ctx->ring_words(), EW = compact ? ctx->enc_words() / 2 : ctx->enc_words();
   int tile_idx = 0;
   for (size_t t0 = 0; t0 < count; t0 += tile, tile_idx++) {
     const int buf = tile_idx & 1;
@@ -158,7 +167,7 @@ static void encode_vector(rs_ctx *ctx, LinRows lf, const uint64_t *d_sk, size_t 
     for (int r = 0; r < lf.R; r++) part.rows[r] = lf.rows[r] + t0 * S;
     uint64_t *d_tile = stage + (size_t)buf * tile * EW;
     if (tile_idx >= 2) RS_HIP(hipStreamWaitEvent(st, kg.ev_drained[buf], 0));  // the copy of tile - 2 has left the buffer
-    encode_linear(ctx, part, d_sk, tt, seed + t0, d_tile, st);
+    encode_linear(ctx, part, d_sk, tt, seed + t0, pub + t0, compact, d_tile, st);
     RS_HIP(hipEventRecord(kg.ev_encoded[buf], st));
     RS_HIP(hipStreamWaitEvent(kg.copy_stream, kg.ev_encoded[buf], 0));
     RS_HIP(hipMemcpyAsync(dst + t0 * EW, d_tile, tt * EW * sizeof(uint64_t), hipMemcpyDeviceToHost, kg.copy_stream));
@@ -200,10 +209,11 @@ struct KeyVector {
 };
 
 // SCHEME 0: groth16 (trap = alpha, beta, delta), 1: rinocchio (trap = alpha, beta, r_v, r_w, r_y).
-// dst: the scheme's outputs in the order of h_seeds.
+// dst: the scheme's outputs in the order of h_seeds.  h_pub != nullptr: a seeded key (seeded.h) -- the three vectors compact,
+// a of every element from the public stream h_pub[v] + k.
 template <int SCHEME>
 static void keygen_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, const uint64_t *const *trap, const uint64_t *d_sk,
-                       const uint64_t *h_seeds, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st) {
+                       const uint64_t *h_seeds, const uint64_t *h_pub, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st) {
   constexpr int NV = SCHEME == 0 ? 5 : 6, NT = SCHEME == 0 ? 3 : 5;
   RS_REQUIRE(cs && d_s && d_sk && h_seeds, "null argument");
   for (int e = 0; e < NT; e++) RS_REQUIRE(trap[e] != nullptr, "null argument");
@@ -219,6 +229,11 @@ static void keygen_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, cons
     for (int w = 0; w < v; w++)
       RS_REQUIRE(!ranges_meet(h_seeds[v], len[v], h_seeds[w], len[w]),
                  "seed ranges of two key vectors intersect: their elements would share the encryption randomness");
+  if (h_pub)
+    for (int v = 0; v < NV; v++)
+      for (int w = 0; w < v; w++)
+        RS_REQUIRE(!ranges_meet(h_pub[v], len[v], h_pub[w], len[w]),
+                   "public seed ranges of two key vectors intersect: their elements would share the polynomial a");
   if (host_key && tile == 0) tile = KEYGEN_HOST_TILE;
   if (host_key) RS_REQUIRE(tile * (size_t)ctx->L < ((size_t)1 << 31), "tile too large");
 
@@ -270,7 +285,7 @@ static void keygen_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, cons
     uint64_t *stage = nullptr;
     if (host_key) {
       KeygenState &kg = ctx->keygen;
-      stage = (uint64_t *)ws_get(ctx, WS_KEYGEN_STAGE, 2 * tile * ctx->enc_words() * sizeof(uint64_t));
+      stage = (uint64_t *)ws_get(ctx, WS_KEYGEN_STAGE, 2 * tile * (h_pub ? ctx->enc_words() / 2 : ctx->enc_words()) * sizeof(uint64_t));
       if (!kg.copy_stream) RS_HIP(hipStreamCreateWithFlags(&kg.copy_stream, hipStreamNonBlocking));
       for (int b = 0; b < 2; b++) {  // each by its own null test: a call that failed half way is completed by the next
         if (!kg.ev_encoded[b]) RS_HIP(hipEventCreateWithFlags(&kg.ev_encoded[b], hipEventDisableTiming));
@@ -278,9 +293,19 @@ static void keygen_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, cons
       }
     }
     for (int v = 0; v < NV; v++)
-      encode_vector(ctx, vec[v].lf, d_sk, vec[v].count, h_seeds[v], vec[v].dst, host_key && vec[v].big, tile, stage, st);
+      encode_vector(ctx, vec[v].lf, d_sk, vec[v].count, h_seeds[v], h_pub ? h_pub[v] : h_seeds[v], h_pub && vec[v].big, vec[v].dst,
+                    host_key && vec[v].big, tile, stage, st);
     RS_HIP(hipStreamSynchronize(st));
   }
+}
+
+
+void keygen_run_scheme(int scheme, rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, const uint64_t *const *trap, const uint64_t *d_sk,
+                       const uint64_t *h_seeds, const uint64_t *h_pub, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st) {
+  if (scheme == 0)
+    keygen_run<0>(ctx, cs, d_s, trap, d_sk, h_seeds, h_pub, dst, host_key, tile, st);
+  else
+    keygen_run<1>(ctx, cs, d_s, trap, d_sk, h_seeds, h_pub, dst, host_key, tile, st);
 }
 
 }  // namespace rs
@@ -296,7 +321,7 @@ int rs_groth16_keygen(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, const
   RS_REQUIRE(out != nullptr, "null argument");
   const uint64_t *trap[3] = {d_alpha, d_beta, d_delta};
   uint64_t *dst[5] = {out->s_pows, out->delta_ts, out->delta_mid, out->d_alpha, out->d_beta};
-  keygen_run<0>(ctx, cs, d_s, trap, d_sk, h_seeds, dst, out->host_key != 0, out->tile, S(stream));
+  keygen_run<0>(ctx, cs, d_s, trap, d_sk, h_seeds, nullptr, dst, out->host_key != 0, out->tile, S(stream));
   RS_API_END
 }
 
@@ -307,7 +332,7 @@ int rs_rinocchio_keygen(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, con
   RS_REQUIRE(out != nullptr, "null argument");
   const uint64_t *trap[5] = {d_alpha, d_beta, d_rv, d_rw, d_ry};
   uint64_t *dst[6] = {out->s_pows, out->alpha_s_pows, out->beta_prods, out->d_beta_rv_ts, out->d_beta_rw_ts, out->d_beta_ry_ts};
-  keygen_run<1>(ctx, cs, d_s, trap, d_sk, h_seeds, dst, out->host_key != 0, out->tile, S(stream));
+  keygen_run<1>(ctx, cs, d_s, trap, d_sk, h_seeds, nullptr, dst, out->host_key != 0, out->tile, S(stream));
   RS_API_END
 }
 
@@ -326,7 +351,7 @@ int rs_enc_encode_linear(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *cons
   if (count == 0) return RS_OK;
   RS_REQUIRE(ctx->N_enc <= 16 * 1024, "encoding degree out of range");
   WsScope ws_scope(ctx, S(stream));
-  encode_linear(ctx, lf, d_sk, count, seed, d_enc, S(stream));
+  encode_linear(ctx, lf, d_sk, count, seed, seed, false, d_enc, S(stream));
   RS_HIP(hipStreamSynchronize(S(stream)));
   RS_API_END
 }

@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(256) broadcast_rows_kernel(const uint64_t *__r
 template <class M>
 static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
                           int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
-                          size_t crs_window, const MsmLin *lin, bool crs_on_host) {
+                          size_t crs_window, const MsmLin *lin, bool crs_on_host, const uint64_t *pub_seeds) {
   using Lift = typename ArithOf<M>::Lift;
   constexpr bool FP = std::is_same<M, Mod>::value;
   RS_REQUIRE(n_crs >= 1 && n_crs <= 2, "n_crs must be 1 or 2");
@@ -239,9 +239,15 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   // Host-resident key (crs_on_host: d_crs are HOST pointers -- a proving key larger than HBM, e.g. the 384 GiB key of the
   // 2^16-constraint headline on one GPU): the term tiles are streamed through two device staging buffers; the copy of
   // tile k+1 runs on its own stream under the kernels of tile k (pinned host memory, rs_host_alloc, for real overlap).
-  uint64_t *stage = nullptr;
+  // Seeded key (pub_seeds: the vectors are COMPACT, c0 only, seeded.h): every tile is expanded into a staging buffer by
+  // expand_seeded_tile_kernel on `st`, between ev_copied and the tile's kernels, and everything downstream reads the staging
+  // buffer as it does for a host-resident key.  A host-resident seeded key lands in two compact buffers behind the staging
+  // buffers (half their size) first; a device-resident one is expanded from where it lies, with no copy and no event.
+  const bool seeded = pub_seeds != nullptr, staged = crs_on_host || seeded;
+  const size_t key_words = seeded ? enc_words / 2 : enc_words;  // words of a stored element
+  uint64_t *stage = nullptr, *land = nullptr;
   size_t stage_words = 0;
-  if (crs_on_host) {
+  if (staged) {
     tile_terms = std::min<size_t>(tile_terms, (size_t)std::max(1, g_tune.msm_host_tile));
     if (crs_window) {
       size_t p2 = 1;
@@ -249,7 +255,11 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
       tile_terms = std::min(p2, crs_window);  // may no longer divide the window: issue_copy splits a tile at the wrap
     }
     stage_words = tile_terms * enc_words;
-    stage = (uint64_t *)ws_get(ctx, WS_SMALL, (size_t)2 * n_crs * stage_words * sizeof(uint64_t));
+    const size_t land_words = seeded && crs_on_host ? tile_terms * key_words : 0;
+    stage = (uint64_t *)ws_get(ctx, WS_SMALL, (size_t)2 * n_crs * (stage_words + land_words) * sizeof(uint64_t));
+    land = stage + (size_t)2 * n_crs * stage_words;
+  }
+  if (crs_on_host) {
     if (!sc.copy_stream) RS_HIP(hipStreamCreateWithFlags(&sc.copy_stream, hipStreamNonBlocking));
     for (int b = 0; b < 2; b++) {  // each by its own null test: a call that failed half way is completed by the next
       if (!sc.ev_copied[b]) RS_HIP(hipEventCreateWithFlags(&sc.ev_copied[b], hipEventDisableTiming));
@@ -260,7 +270,10 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     RS_HIP(hipEventRecord(sc.ev_freed[1], st));
   }
   auto stage_at = [&](int buf, int c) { return stage + ((size_t)buf * n_crs + c) * stage_words; };
-  auto issue_copy = [&](int tile, size_t t0) {  // tile -> staging buffer tile % 2, on the copy stream
+  auto land_at = [&](int buf, int c) {  // where the copy of a tile arrives: the staging buffer itself, or the compact buffer of a seeded key
+    return seeded ? land + ((size_t)buf * n_crs + c) * (stage_words / 2) : stage_at(buf, c);
+  };
+  auto issue_copy = [&](int tile, size_t t0) {  // tile -> staging (landing) buffer tile % 2, on the copy stream
     const int buf = tile & 1;
     const size_t tt = std::min(tile_terms, Tmax - t0);
     RS_HIP(hipStreamWaitEvent(sc.copy_stream, sc.ev_freed[buf], 0));
@@ -269,11 +282,11 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     const size_t o0 = crs_window ? t0 % crs_window : t0;
     const size_t first = crs_window ? std::min(tt, crs_window - o0) : tt;
     for (int c = 0; c < n_crs; c++) {
-      RS_HIP(hipMemcpyAsync(stage_at(buf, c), d_crs[c] + o0 * enc_words, first * enc_words * sizeof(uint64_t), hipMemcpyHostToDevice,
+      RS_HIP(hipMemcpyAsync(land_at(buf, c), d_crs[c] + o0 * key_words, first * key_words * sizeof(uint64_t), hipMemcpyHostToDevice,
                             sc.copy_stream));
       for (size_t done = first; done < tt;) {  // wrapped remainder (several rounds if the tile exceeds the window)
         const size_t part = std::min(tt - done, crs_window);
-        RS_HIP(hipMemcpyAsync(stage_at(buf, c) + done * enc_words, d_crs[c], part * enc_words * sizeof(uint64_t), hipMemcpyHostToDevice,
+        RS_HIP(hipMemcpyAsync(land_at(buf, c) + done * key_words, d_crs[c], part * key_words * sizeof(uint64_t), hipMemcpyHostToDevice,
                               sc.copy_stream));
         done += part;
       }
@@ -282,7 +295,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   };
   int cur_tile = 0;
   auto crs_at = [&](int c, size_t t0) -> const uint64_t * {
-    if (crs_on_host) return stage_at(cur_tile & 1, c);
+    if (staged) return stage_at(cur_tile & 1, c);
     return d_crs[c] + (crs_window ? t0 % crs_window : t0) * enc_words;
   };
   // mac_kernel_v4 (two key vectors) runs ONE workgroup per CU: half the workgroup slots, half the chunks (measured at the
@@ -345,6 +358,10 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
       if (t0 + tile_terms < Tmax) issue_copy(tile_idx + 1, t0 + tile_terms);  // under this tile's kernels
       RS_HIP(hipStreamWaitEvent(st, sc.ev_copied[tile_idx & 1], 0));
     }
+    if (seeded)  // c1 of the tile's elements from their STORED indices (t0 + i) % crs_window; the landing buffer is the tile in order
+      for (int c = 0; c < n_crs; c++)
+        expand_seeded_run(ctx, crs_on_host ? land_at(tile_idx & 1, c) : d_crs[c], crs_on_host, pub_seeds[c], t0, crs_window, tt,
+                          stage_at(tile_idx & 1, c), st);
     double rows_in = 0;  // coefficient rows (term, limb) read by this tile
     for (int v = 0; v < n_vecs; v++) rows_in += (double)(vecs[v].T > t0 ? std::min(tt, vecs[v].T - t0) : 0) * L;
     {
@@ -588,9 +605,9 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
 
 void msm_run(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
              int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
-             size_t crs_window, const MsmLin *lin, bool crs_on_host) {
-  RS_DISPATCH_ARITH(ctx, (msm_run_arith<Mod>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host)),
-                    (msm_run_arith<ModI>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host)));
+             size_t crs_window, const MsmLin *lin, bool crs_on_host, const uint64_t *pub_seeds) {
+  RS_DISPATCH_ARITH(ctx, (msm_run_arith<Mod>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host, pub_seeds)),
+                    (msm_run_arith<ModI>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host, pub_seeds)));
 }
 // can a call with linear-form vectors be served? (FP64 context on the wide plaintext kernel)
 bool msm_supports_lin(const rs_ctx *ctx) {

@@ -73,24 +73,12 @@ chain_kernel(uint64_t *__restrict__ asg, size_t m, int N, int L, const M *__rest
   }
 }
 
-}  // namespace rs
-
-using namespace rs;
-
-extern "C" {
-
-int rs_groth16_prove(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *d_assignment,
-                     uint64_t *d_proof, int *h_empty, rs_stream stream) {
-  return rs_groth16_prove_kinds(ctx, cs, pk, d_assignment, nullptr, d_proof, h_empty, stream);
-}
-
-int rs_groth16_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *d_assignment,
-                           const uint8_t *h_assignment_kinds, uint64_t *d_proof, int *h_empty, rs_stream stream) {
-  RS_API_BEGIN_CTX(ctx)
+// groth16::prover (groth16.tcc:70-115).  pub: nullptr, or the public seeds of s_pows, delta_ts, delta_mid of a seeded key.
+void groth16_prove_run(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *pub, const uint64_t *d_assignment,
+                       const uint8_t *h_assignment_kinds, uint64_t *d_proof, int *h_empty, hipStream_t st) {
   RS_REQUIRE(ctx && cs && pk && d_assignment && d_proof, "null argument");
   RS_REQUIRE(pk->d_s_pows && pk->d_delta_ts && pk->d_alpha && pk->d_beta, "incomplete proving key");
-  WsScope ws_scope(ctx, S(stream));
-  hipStream_t st = S(stream);
+  WsScope ws_scope(ctx, st);
   const size_t m = cs->m, rw = ctx->ring_words(), ew = ctx->enc_words();
   const size_t n_aux = cs->n_vars - cs->n_inputs;
   RS_REQUIRE(n_aux == 0 || pk->d_delta_mid, "delta_mid missing");
@@ -130,10 +118,10 @@ int rs_groth16_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *
         ln[w].T = m;
       }
       rs_msm_vec v[2] = {{A_mid, nullptr, m, 0}, {B_mid, nullptr, m, 1}};
-      msm_run(ctx, crs, 1, m + 1, v, 2, 2, d_proof, add, nullptr, st, pk->window, ln, host_key);
+      msm_run(ctx, crs, 1, m + 1, v, 2, 2, d_proof, add, nullptr, st, pk->window, ln, host_key, pub);
     } else {
       rs_msm_vec v[4] = {{A_io, nullptr, m, 0}, {A_mid, nullptr, m, 0}, {B_io, nullptr, m, 1}, {B_mid, nullptr, m, 1}};
-      msm_run(ctx, crs, 1, m + 1, v, 4, 2, d_proof, add, nullptr, st, pk->window, nullptr, host_key);
+      msm_run(ctx, crs, 1, m + 1, v, 4, 2, d_proof, add, nullptr, st, pk->window, nullptr, host_key, pub);
     }
   }
   // C = <delta_ts, H> (+ <delta_mid, aux>)                                 (groth16.tcc:105-112)
@@ -143,13 +131,13 @@ int rs_groth16_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *
     const uint64_t *crs[1] = {pk->d_delta_mid};
     // the wires as the caller holds them: a Scalar-1 wire passes its key element through (seal_ring.tcc:525-527)
     rs_msm_vec v{d_assignment + cs->n_inputs * rw, h_assignment_kinds ? h_assignment_kinds + cs->n_inputs : nullptr, n_aux, 0};
-    msm_run(ctx, crs, 1, n_aux, &v, 1, 1, C, nullptr, h_empty ? &used_aux : nullptr, st, pk->window, nullptr, host_key);
+    msm_run(ctx, crs, 1, n_aux, &v, 1, 1, C, nullptr, h_empty ? &used_aux : nullptr, st, pk->window, nullptr, host_key, pub ? pub + 2 : nullptr);
   }
   {
     const uint64_t *crs[1] = {pk->d_delta_ts};
     rs_msm_vec v{H, nullptr, m + 1, 0};
     const uint64_t *add[1] = {n_aux ? C : nullptr};
-    msm_run(ctx, crs, 1, m + 1, &v, 1, 1, C, add, h_empty ? &used_h : nullptr, st, pk->window, nullptr, host_key);
+    msm_run(ctx, crs, 1, m + 1, &v, 1, 1, C, add, h_empty ? &used_h : nullptr, st, pk->window, nullptr, host_key, pub ? pub + 1 : nullptr);
   }
   pt.mark(2);
   pt.finish();
@@ -158,24 +146,16 @@ int rs_groth16_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *
     h_empty[0] = h_empty[1] = 0;  // alpha / beta are always added
     h_empty[2] = (used_h == 0 && used_aux == 0) ? 1 : 0;
   }
-  RS_API_END
 }
 
-int rs_rinocchio_prove(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *d_assignment,
-                       const uint64_t *d_d1, const uint64_t *d_d2, const uint64_t *d_d3, uint64_t *d_proof, int *h_empty,
-                       rs_stream stream) {
-  return rs_rinocchio_prove_kinds(ctx, cs, pk, d_assignment, nullptr, d_d1, d_d2, d_d3, d_proof, h_empty, stream);
-}
-
-int rs_rinocchio_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *d_assignment,
-                             const uint8_t *h_assignment_kinds, const uint64_t *d_d1, const uint64_t *d_d2, const uint64_t *d_d3,
-                             uint64_t *d_proof, int *h_empty, rs_stream stream) {
-  RS_API_BEGIN_CTX(ctx)
+// rinocchio::prover (rinocchio.tcc:75-190).  pub: nullptr, or the public seeds of s_pows, alpha_s_pows, beta_prods.
+void rinocchio_prove_run(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *pub, const uint64_t *d_assignment,
+                         const uint8_t *h_assignment_kinds, const uint64_t *d_d1, const uint64_t *d_d2, const uint64_t *d_d3,
+                         uint64_t *d_proof, int *h_empty, hipStream_t st) {
   RS_REQUIRE(ctx && cs && pk && d_assignment && d_proof, "null argument");
   RS_REQUIRE(pk->d_s_pows && pk->d_alpha_s_pows, "incomplete proving key");
   RS_REQUIRE((d_d1 && d_d2 && d_d3) || (!d_d1 && !d_d2 && !d_d3), "d1,d2,d3 must be all set or all null");
-  WsScope ws_scope(ctx, S(stream));
-  hipStream_t st = S(stream);
+  WsScope ws_scope(ctx, st);
   const size_t m = cs->m, rw = ctx->ring_words(), ew = ctx->enc_words();
   const size_t n_aux = cs->n_vars - cs->n_inputs;
   const bool zk = d_d1 != nullptr;  // rinocchio.tcc:81-90
@@ -203,7 +183,7 @@ int rs_rinocchio_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_
     const uint64_t *crs[2] = {pk->d_s_pows, pk->d_alpha_s_pows};
     rs_msm_vec v[5] = {{A_mid, nullptr, m, 0}, {B_mid, nullptr, m, 1}, {C_mid, nullptr, m, 2}, {H, nullptr, m + 1, 3},
                        {dZ, zkinds.data(), m + 1, 4, 1}};
-    msm_run(ctx, crs, 2, m + 1, v, 5, 5, mo, nullptr, used, st, pk->window, nullptr, pk->host_key != 0);
+    msm_run(ctx, crs, 2, m + 1, v, 5, 5, mo, nullptr, used, st, pk->window, nullptr, pk->host_key != 0, pub);
   }
   auto slot = [&](int c, int g) { return mo + ((size_t)c * 5 + g) * ew; };
   int empty[9];
@@ -237,7 +217,7 @@ int rs_rinocchio_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_
     size_t used_f = 0;
     const uint64_t *crs[1] = {pk->d_beta_prods};
     rs_msm_vec v{d_assignment + cs->n_inputs * rw, h_assignment_kinds ? h_assignment_kinds + cs->n_inputs : nullptr, n_aux, 0};
-    msm_run(ctx, crs, 1, n_aux, &v, 1, 1, F, nullptr, &used_f, st, pk->window, nullptr, pk->host_key != 0);
+    msm_run(ctx, crs, 1, n_aux, &v, 1, 1, F, nullptr, &used_f, st, pk->window, nullptr, pk->host_key != 0, pub ? pub + 2 : nullptr);
     empty[8] = used_f == 0;
     if (zk) {
       add_scaled(F, &empty[8], pk->d_beta_rv_ts, d_d1);
@@ -249,6 +229,37 @@ int rs_rinocchio_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_
   pt.finish();
   RS_HIP(hipStreamSynchronize(st));  // zkinds is a host temporary referenced by async copies
   if (h_empty) memcpy(h_empty, empty, sizeof(empty));
+}
+
+}  // namespace rs
+
+using namespace rs;
+
+extern "C" {
+
+int rs_groth16_prove(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *d_assignment,
+                     uint64_t *d_proof, int *h_empty, rs_stream stream) {
+  return rs_groth16_prove_kinds(ctx, cs, pk, d_assignment, nullptr, d_proof, h_empty, stream);
+}
+
+int rs_groth16_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *d_assignment,
+                           const uint8_t *h_assignment_kinds, uint64_t *d_proof, int *h_empty, rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  groth16_prove_run(ctx, cs, pk, nullptr, d_assignment, h_assignment_kinds, d_proof, h_empty, S(stream));
+  RS_API_END
+}
+
+int rs_rinocchio_prove(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *d_assignment,
+                       const uint64_t *d_d1, const uint64_t *d_d2, const uint64_t *d_d3, uint64_t *d_proof, int *h_empty,
+                       rs_stream stream) {
+  return rs_rinocchio_prove_kinds(ctx, cs, pk, d_assignment, nullptr, d_d1, d_d2, d_d3, d_proof, h_empty, stream);
+}
+
+int rs_rinocchio_prove_kinds(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *d_assignment,
+                             const uint8_t *h_assignment_kinds, const uint64_t *d_d1, const uint64_t *d_d2, const uint64_t *d_d3,
+                             uint64_t *d_proof, int *h_empty, rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  rinocchio_prove_run(ctx, cs, pk, nullptr, d_assignment, h_assignment_kinds, d_d1, d_d2, d_d3, d_proof, h_empty, S(stream));
   RS_API_END
 }
 

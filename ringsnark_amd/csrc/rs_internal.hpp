@@ -143,7 +143,7 @@ enum WsSlot {
   WS_COLUMNS,        // witness_chunk, interpolate_arith: the column-major vectors of a chunk, [vectors][columns][M].  Two entry points.
   WS_BC_SPECTRA,     // bc_h, bc2_h: spectra of the second operand's blocks, [columns][2M | 4M].  A plan is either bc or bc2.
   WS_SMALL,          // rs_ring_inv, rs_ring_is_zero, normalised_len (poly.hip), rs_r1cs_check, io_eval_run: flag / report words (io_eval_run: + the constants c_j from byte 256);
-                     // msm_run with a host-resident key: the two staging buffers of the key tiles.  vk_create calls rs_ring_inv and then io_eval_at: two scopes, one after the
+                     // msm_run with a host-resident or a seeded key: the two staging buffers of the key tiles (+ the two compact landing buffers of a host-resident seeded key).  vk_create calls rs_ring_inv and then io_eval_at: two scopes, one after the
                      // other.  normalised_len synchronises before it returns, so its three calls in one scope each take a dead pointer's place.  The provers reach msm_run
                      // after witness_run, which does not take this slot, and nothing else in a prover's scope does.
   WS_PROVER_VECS,    // rs_groth16_prove_kinds, rs_rinocchio_prove_kinds: the witness map's output vectors, [4m+1 | 5m+1] ring elements.  Two entry points.
@@ -359,7 +359,7 @@ void launch_ntt_int(rs_ctx *ctx, const NttTableI &t, uint64_t *d_data, size_t ba
 // msm.hip.  msm_run: the caller holds the context's WsScope
 void msm_run(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
              int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
-             size_t crs_window, const MsmLin *lin = nullptr, bool crs_on_host = false);
+             size_t crs_window, const MsmLin *lin = nullptr, bool crs_on_host = false, const uint64_t *pub_seeds = nullptr);
 bool msm_supports_lin(const rs_ctx *ctx);
 void batch_encode_run(rs_ctx *ctx, const uint64_t *d_rings, uint64_t *d_plain, size_t count, hipStream_t st);
 void enc_add_run(rs_ctx *ctx, uint64_t *dst, const uint64_t *x, const uint64_t *y, size_t count, hipStream_t st);
@@ -385,6 +385,22 @@ __device__ __forceinline__ uint64_t splitmix_at(uint64_t seed, uint64_t k) {
   return z ^ (z >> 31);
 }
 #endif
+// seeded.hip.  count full-format elements at dst from compact c0 blocks: c0 copied, c1 regenerated (seeded.h).  Element i has
+// STORED index (first + i) % window (window == 0: first + i), which numbers its stream; its c0 is element i of `c0`
+// (linear: a landing buffer, a caller's slice) or element <stored index> of it (the whole vector of a device-resident key).
+void expand_seeded_run(rs_ctx *ctx, const uint64_t *c0, bool linear, uint64_t pub_seed, size_t first, size_t window, size_t count,
+                       uint64_t *dst, hipStream_t st);
+// keygen.hip.  The body of the generators: scheme 0 groth16 (5 seeds, 3 trapdoor elements), 1 rinocchio (6, 5); dst in the
+// order of h_seeds; h_pub != nullptr: a seeded key.  Takes the context's WsScope itself.
+void keygen_run_scheme(int scheme, rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, const uint64_t *const *trap, const uint64_t *d_sk,
+                       const uint64_t *h_seeds, const uint64_t *h_pub, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st);
+// prover.hip.  The bodies of rs_groth16_prove_kinds / rs_rinocchio_prove_kinds; pub != nullptr: the three vectors of pk are
+// compact and pub holds their public seeds (seeded.h).  They take the context's WsScope themselves.
+void groth16_prove_run(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *pub, const uint64_t *d_assignment,
+                       const uint8_t *h_assignment_kinds, uint64_t *d_proof, int *h_empty, hipStream_t st);
+void rinocchio_prove_run(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *pub, const uint64_t *d_assignment,
+                         const uint8_t *h_assignment_kinds, const uint64_t *d_d1, const uint64_t *d_d2, const uint64_t *d_d3,
+                         uint64_t *d_proof, int *h_empty, hipStream_t st);
 // witness_plan.hip
 const uint64_t *witness_Z_rows(rs_ctx *ctx, size_t m);
 void witness_plans_destroy(rs_ctx *ctx);  // every plan of the context (rs_ctx_destroy)

@@ -315,10 +315,45 @@ class Device:
         assert len(seeds) == n, (len(seeds), n)
         return (C.c_uint64 * n)(*[(int(x) * 65537) % 2**64 for x in seeds])
 
-    def _key_vector(self, count, host):
+    def _key_vector(self, count, host, seeded=False):
+        """seeded: the compact layout [count][L][K][N_enc] (ringsnark_amd/seeded.h)"""
         if host:
-            return self.host_alloc(max(count, 1) * self.enc_words)
-        return self.enc_empty(count)
+            return self.host_alloc(max(count, 1) * (self.enc_words // 2 if seeded else self.enc_words))
+        return self.c0_empty(count) if seeded else self.enc_empty(count)
+
+    def c0_empty(self, *lead):
+        return torch.empty(tuple(lead) + (self.L, self.K, self.N_enc), dtype=torch.int64, device=self.device)
+
+    def _public_seeds(self, seeds, pub_seeds, lens, allow_shared_seeds):
+        """(the public seeds of a seeded key in enc_encode's convention, their words for the C interface).  None: drawn from
+        the `secrets` module, one 64-bit base and KEYGEN_SEED_STRIDE between the vectors.  A public stream that is also a
+        private one hands the error polynomial to the prover (seeded.h): ValueError unless allow_shared_seeds (tests)."""
+        n = len(lens)
+        if pub_seeds is None:
+            import secrets
+            base = secrets.randbits(64)
+            pub_seeds = [(base + v * self.KEYGEN_SEED_STRIDE) % 2**64 for v in range(n)]
+        elif isinstance(pub_seeds, int):
+            pub_seeds = [pub_seeds + v * self.KEYGEN_SEED_STRIDE for v in range(n)]
+        pub_seeds = [int(x) for x in pub_seeds]
+        assert len(pub_seeds) == n, (len(pub_seeds), n)
+        words, priv = self._keygen_seeds(pub_seeds, n), self._keygen_seeds(seeds, n)
+        meet = lambda a, la, b, lb: la and lb and ((b - a) % 2**64 < la or (a - b) % 2**64 < lb)
+        if not allow_shared_seeds and any(meet(words[v], lens[v], priv[w], lens[w]) for v in range(n) for w in range(n)):
+            raise ValueError("a public seed of a seeded key is also a private seed: the prover could compute the error polynomials "
+                             "(pass allow_shared_seeds=True in tests only)")
+        return pub_seeds, words
+
+    def enc_expand_seeded(self, c0, pub_seed, first=0):
+        """rs_enc_expand_seeded: compact elements c0 [count][L][K][N_enc] -> full elements [count][L][2][K][N_enc], c0 copied
+        and c1 regenerated from the public stream of stored index first + i (pub_seed in enc_encode's convention).  With the
+        c0 blocks of enc_encode(sk, rings, seed) and pub_seed = seed: those elements."""
+        assert c0.is_contiguous()
+        count = self._count(c0, self.enc_words // 2)
+        out = self.enc_empty(count) if c0.dim() > 3 else self.enc_empty()
+        _lib.check(self.lib.rs_enc_expand_seeded(self.h, _ptr(c0), C.c_uint64((pub_seed * 65537) % 2**64), first, count, _ptr(out),
+                                                 self.stream()))
+        return out
 
     def enc_encode_linear(self, sk, rows, seed, coefs=None):
         """rs_enc_encode_linear: E(sum_r coefs[r] * rows[r][k]) for every k; rows: one to three tensors [count][L][N], coefs:
@@ -334,37 +369,57 @@ class Device:
                                                  self.stream()))
         return out
 
-    def groth16_keygen(self, dcs, vk, seeds=None, host=False, tile=0):
+    def groth16_keygen(self, dcs, vk, seeds=None, host=False, tile=0, seeded=False, pub_seeds=None, allow_shared_seeds=False):
         """groth16::generator (groth16.tcc:5-66) on the device: the proving key of the trapdoor `vk` (the dict groth16_vk
         takes: s, alpha, beta, gamma, delta, sk), as the dict groth16_prove accepts.  seeds: None, one integer, or five
         (s_pows, delta_ts, delta_mid, alpha, beta) in enc_encode's convention; their ranges must not intersect.
-        host: the three vectors are HostWords (a key larger than HBM), encoded in tiles of `tile` elements."""
+        host: the three vectors are HostWords (a key larger than HBM), encoded in tiles of `tile` elements.
+        seeded: a seeded key (ringsnark_amd/seeded.h) -- the three vectors compact [count][L][K][N_enc] (half the size), and
+        "pub_seeds": the five public seeds their c1 halves are regenerated from (pub_seeds: None = drawn from `secrets`, one
+        integer, or five); groth16_prove and enc_expand_seeded take them from the dict."""
         t = {k: self._vk_part(vk[k]) for k in ("s", "alpha", "beta", "delta", "sk")}
-        self.sync()
         m, n_aux = dcs.m, dcs.n_vars - dcs.n_inputs
-        pk = dict(s_pows=self._key_vector(m + 1, host), delta_ts=self._key_vector(m + 1, host),
-                  delta_mid=self._key_vector(n_aux, host) if n_aux else None, alpha=self.enc_empty(), beta=self.enc_empty())
+        if seeded:
+            pub, pub_words = self._public_seeds(seeds, pub_seeds, [m + 1, m + 1, n_aux, 1, 1], allow_shared_seeds)
+        self.sync()
+        pk = dict(s_pows=self._key_vector(m + 1, host, seeded), delta_ts=self._key_vector(m + 1, host, seeded),
+                  delta_mid=self._key_vector(n_aux, host, seeded) if n_aux else None, alpha=self.enc_empty(), beta=self.enc_empty())
         addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
-        out = _lib.Groth16KeyOut(addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk["delta_mid"]), pk["alpha"].data_ptr(),
-                                 pk["beta"].data_ptr(), 1 if host else 0, tile)
-        _lib.check(self.lib.rs_groth16_keygen(self.h, dcs.h, _ptr(t["s"]), _ptr(t["alpha"]), _ptr(t["beta"]), _ptr(t["delta"]),
-                                              _ptr(t["sk"]), self._keygen_seeds(seeds, 5), C.byref(out), self.stream()))
+        members = (addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk["delta_mid"]), pk["alpha"].data_ptr(), pk["beta"].data_ptr(),
+                   1 if host else 0, tile)
+        args = [self.h, dcs.h, _ptr(t["s"]), _ptr(t["alpha"]), _ptr(t["beta"]), _ptr(t["delta"]), _ptr(t["sk"]), self._keygen_seeds(seeds, 5)]
+        if seeded:
+            out = _lib.Groth16SeededKeyOut(*members)
+            _lib.check(self.lib.rs_groth16_keygen_seeded(*args, pub_words, C.byref(out), self.stream()))
+            pk["pub_seeds"] = pub
+        else:
+            out = _lib.Groth16KeyOut(*members)
+            _lib.check(self.lib.rs_groth16_keygen(*args, C.byref(out), self.stream()))
         return pk
 
-    def rinocchio_keygen(self, dcs, vk, seeds=None, host=False, tile=0):
+    def rinocchio_keygen(self, dcs, vk, seeds=None, host=False, tile=0, seeded=False, pub_seeds=None, allow_shared_seeds=False):
         """rinocchio::generator (rinocchio.tcc:5-72): the dict rinocchio_prove accepts, from the dict rinocchio_vk takes.
-        seeds: s_pows, alpha_s_pows, beta_prods, beta_rv_ts, beta_rw_ts, beta_ry_ts."""
+        seeds: s_pows, alpha_s_pows, beta_prods, beta_rv_ts, beta_rw_ts, beta_ry_ts.  seeded, pub_seeds, allow_shared_seeds:
+        as in groth16_keygen (six public seeds)."""
         t = {k: self._vk_part(vk[k]) for k in ("s", "alpha", "beta", "r_v", "r_w", "r_y", "sk")}
-        self.sync()
         m, n_aux = dcs.m, dcs.n_vars - dcs.n_inputs
-        pk = dict(s_pows=self._key_vector(m + 1, host), alpha_s_pows=self._key_vector(m + 1, host),
-                  beta_prods=self._key_vector(n_aux, host) if n_aux else None, beta_rv_ts=self.enc_empty(),
+        if seeded:
+            pub, pub_words = self._public_seeds(seeds, pub_seeds, [m + 1, m + 1, n_aux, 1, 1, 1], allow_shared_seeds)
+        self.sync()
+        pk = dict(s_pows=self._key_vector(m + 1, host, seeded), alpha_s_pows=self._key_vector(m + 1, host, seeded),
+                  beta_prods=self._key_vector(n_aux, host, seeded) if n_aux else None, beta_rv_ts=self.enc_empty(),
                   beta_rw_ts=self.enc_empty(), beta_ry_ts=self.enc_empty())
         addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
-        out = _lib.RinocchioKeyOut(addr(pk["s_pows"]), addr(pk["alpha_s_pows"]), addr(pk["beta_prods"]), pk["beta_rv_ts"].data_ptr(),
-                                   pk["beta_rw_ts"].data_ptr(), pk["beta_ry_ts"].data_ptr(), 1 if host else 0, tile)
-        _lib.check(self.lib.rs_rinocchio_keygen(self.h, dcs.h, *[_ptr(t[k]) for k in ("s", "alpha", "beta", "r_v", "r_w", "r_y", "sk")],
-                                                self._keygen_seeds(seeds, 6), C.byref(out), self.stream()))
+        members = (addr(pk["s_pows"]), addr(pk["alpha_s_pows"]), addr(pk["beta_prods"]), pk["beta_rv_ts"].data_ptr(),
+                   pk["beta_rw_ts"].data_ptr(), pk["beta_ry_ts"].data_ptr(), 1 if host else 0, tile)
+        args = [self.h, dcs.h] + [_ptr(t[k]) for k in ("s", "alpha", "beta", "r_v", "r_w", "r_y", "sk")] + [self._keygen_seeds(seeds, 6)]
+        if seeded:
+            out = _lib.RinocchioSeededKeyOut(*members)
+            _lib.check(self.lib.rs_rinocchio_keygen_seeded(*args, pub_words, C.byref(out), self.stream()))
+            pk["pub_seeds"] = pub
+        else:
+            out = _lib.RinocchioKeyOut(*members)
+            _lib.check(self.lib.rs_rinocchio_keygen(*args, C.byref(out), self.stream()))
         return pk
 
     # ---- 8(f) f4
@@ -435,16 +490,18 @@ class Device:
                                              C.byref(used) if want_used else None, self.stream()))
         return out, int(used.value)
 
-    def msm(self, crs_list, vecs, n_groups, want_used=False, crs_len=None, window=0):
+    def msm(self, crs_list, vecs, n_groups, want_used=False, crs_len=None, window=0, pub_seeds=None):
         """vecs: list of (coeff tensor [T][L][N], kinds or None, group) or, for a SLOT-CONSTANT vector (one value per
         (term, limb) in every slot: coefficients_for_Z), (tensor [T][L], kinds, group, True).  window != 0: the CRS tensors hold
         `window` elements and logical element t is read from t % window (crs_len = logical length).
-        CRS vectors given as HostWords (host_alloc) are streamed from host memory (rs_msm_hostkey)."""
+        CRS vectors given as HostWords (host_alloc) are streamed from host memory (rs_msm_hostkey).
+        pub_seeds (one per CRS vector, as a seeded key's "pub_seeds" holds them): the CRS vectors are COMPACT (rs_msm_seeded)."""
         n_crs = len(crs_list)
         on_host = isinstance(crs_list[0], HostWords)
         assert all(isinstance(c, HostWords) == on_host for c in crs_list)
+        key_words = self.enc_words if pub_seeds is None else self.enc_words // 2
         if crs_len is None:
-            crs_len = crs_list[0].words // self.enc_words if on_host else self._count(crs_list[0], self.enc_words)
+            crs_len = crs_list[0].words // key_words if on_host else self._count(crs_list[0], key_words)
         crs = (C.c_void_p * n_crs)(*[(c.ptr if on_host else c.data_ptr()) for c in crs_list])
         mv = (_lib.MsmVec * len(vecs))()
         keep = []
@@ -462,6 +519,11 @@ class Device:
                 mv[k].h_kinds = kk.ctypes.data_as(_lib.u8p)
         out = self.enc_empty(n_crs, n_groups)
         used = (C.c_size_t * len(vecs))()
+        if pub_seeds is not None:
+            assert len(pub_seeds) == n_crs
+            _lib.check(self.lib.rs_msm_seeded(self.h, crs, self._keygen_seeds(list(pub_seeds), n_crs), 1 if on_host else 0, n_crs, crs_len,
+                                              window, mv, len(vecs), n_groups, _ptr(out), used if want_used else None, self.stream()))
+            return out, [int(u) for u in used]
         fn = self.lib.rs_msm_hostkey if on_host else self.lib.rs_msm
         _lib.check(fn(self.h, crs, n_crs, crs_len, window, mv, len(vecs), n_groups, _ptr(out), used if want_used else None, self.stream()))
         return out, [int(u) for u in used]
@@ -601,13 +663,19 @@ class Device:
         host_key = isinstance(pk["s_pows"], HostWords)
         addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
         assert all(isinstance(pk[k], HostWords) == host_key for k in ("s_pows", "delta_ts") + (("delta_mid",) if pk.get("delta_mid") is not None else ()))
-        s = _lib.Groth16PK(addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk.get("delta_mid")),
-                           pk["alpha"].data_ptr(), pk["beta"].data_ptr(), window, 1 if host_key else 0)
         proof = self.enc_empty(3)
         empty = (C.c_int * 3)()
         keep, kp = self._kinds(kinds, dcs.n_vars)
-        _lib.check(self.lib.rs_groth16_prove_kinds(self.h, dcs.h, C.byref(s), _ptr(assignment), kp, _ptr(proof),
-                                                   empty if want_empty else None, self.stream()))
+        if "pub_seeds" in pk:  # a seeded key (groth16_keygen(seeded=True)): compact vectors
+            s = _lib.Groth16PKSeeded(addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk.get("delta_mid")),
+                                     (C.c_uint64 * 3)(*self._keygen_seeds(list(pk["pub_seeds"][:3]), 3)), pk["alpha"].data_ptr(),
+                                     pk["beta"].data_ptr(), window, 1 if host_key else 0)
+            prove = self.lib.rs_groth16_prove_seeded
+        else:
+            s = _lib.Groth16PK(addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk.get("delta_mid")),
+                               pk["alpha"].data_ptr(), pk["beta"].data_ptr(), window, 1 if host_key else 0)
+            prove = self.lib.rs_groth16_prove_kinds
+        _lib.check(prove(self.h, dcs.h, C.byref(s), _ptr(assignment), kp, _ptr(proof), empty if want_empty else None, self.stream()))
         return proof, [int(e) for e in empty]
 
     def rinocchio_prove(self, dcs, pk, assignment, d1=None, d2=None, d3=None, window=0, kinds=None, check=False):
@@ -616,13 +684,19 @@ class Device:
             self._require_satisfied(dcs, assignment)
         host_key = isinstance(pk.get("s_pows"), HostWords)
         g = lambda k: None if pk.get(k) is None else (pk[k].ptr if isinstance(pk[k], HostWords) else pk[k].data_ptr())
-        s = _lib.RinocchioPK(g("s_pows"), g("alpha_s_pows"), g("beta_prods"), g("beta_rv_ts"), g("beta_rw_ts"), g("beta_ry_ts"),
-                             window, 1 if host_key else 0)
         proof = self.enc_empty(9)
         empty = (C.c_int * 9)()
         keep, kp = self._kinds(kinds, dcs.n_vars)
-        _lib.check(self.lib.rs_rinocchio_prove_kinds(self.h, dcs.h, C.byref(s), _ptr(assignment), kp, _ptr(d1), _ptr(d2), _ptr(d3),
-                                                     _ptr(proof), empty, self.stream()))
+        if "pub_seeds" in pk:  # a seeded key (rinocchio_keygen(seeded=True)): compact vectors
+            s = _lib.RinocchioPKSeeded(g("s_pows"), g("alpha_s_pows"), g("beta_prods"),
+                                       (C.c_uint64 * 3)(*self._keygen_seeds(list(pk["pub_seeds"][:3]), 3)), g("beta_rv_ts"), g("beta_rw_ts"),
+                                       g("beta_ry_ts"), window, 1 if host_key else 0)
+            prove = self.lib.rs_rinocchio_prove_seeded
+        else:
+            s = _lib.RinocchioPK(g("s_pows"), g("alpha_s_pows"), g("beta_prods"), g("beta_rv_ts"), g("beta_rw_ts"), g("beta_ry_ts"),
+                                 window, 1 if host_key else 0)
+            prove = self.lib.rs_rinocchio_prove_kinds
+        _lib.check(prove(self.h, dcs.h, C.byref(s), _ptr(assignment), kp, _ptr(d1), _ptr(d2), _ptr(d3), _ptr(proof), empty, self.stream()))
         return proof, [int(e) for e in empty]
 
     # ---- measurement / synthetic workloads
