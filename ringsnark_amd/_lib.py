@@ -195,6 +195,15 @@ SEEDED_SIGNATURES = {  # every function of include/ringsnark_amd/seeded.h
     "rs_rinocchio_prove_seeded": (C.c_int, [vp, vp, C.POINTER(RinocchioPKSeeded), vp, u8p, vp, vp, vp, vp, C.POINTER(C.c_int), vp]),
 }
 
+BATCH_SIGNATURES = {  # every function of include/ringsnark_amd/batch.h
+    "rs_groth16_prove_batch": (C.c_int, [vp, vp, C.POINTER(Groth16PK), C.c_int, C.POINTER(vp), u8p, vp, C.POINTER(C.c_int), vp]),
+    "rs_rinocchio_prove_batch": (C.c_int, [vp, vp, C.POINTER(RinocchioPK), C.c_int, C.POINTER(vp), u8p, vp, vp, C.POINTER(C.c_int), vp]),
+    "rs_groth16_prove_batch_seeded": (C.c_int, [vp, vp, C.POINTER(Groth16PKSeeded), C.c_int, C.POINTER(vp), u8p, vp, C.POINTER(C.c_int), vp]),
+    "rs_rinocchio_prove_batch_seeded": (C.c_int, [vp, vp, C.POINTER(RinocchioPKSeeded), C.c_int, C.POINTER(vp), u8p, vp, vp,
+                                                  C.POINTER(C.c_int), vp]),
+    "rs_prove_batch_bytes": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+}
+
 _lib = None
 
 
@@ -209,7 +218,7 @@ def load():
             "the HIP library is the only implementation, there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **VERIFY_SIGNATURES, **KEYGEN_SIGNATURES,
-                              **SEEDED_SIGNATURES}.items():
+                              **SEEDED_SIGNATURES, **BATCH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

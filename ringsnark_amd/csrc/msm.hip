@@ -33,8 +33,12 @@
 #include "rs_internal.hpp"
 #include "msm_plain.hpp"
 #include "msm_mac.hpp"
+#include "../../include/ringsnark_amd/batch.h"
 
 namespace rs {
+
+// groups of one msm_run: every member's four vectors and the shared Z vector of a Rinocchio batch
+constexpr int MSM_MAX_GROUPS = 4 * RS_MAX_BATCH + 1;
 
 static int tile_threads(int logn) { return std::max(64, std::min(1024, (1 << logn) >> 3)); }
 
@@ -93,6 +97,25 @@ static void launch_mac_v3(rs_ctx *ctx, const MacArgs3 &a, hipStream_t st) {
   RS_HIP(hipGetLastError());
 }
 
+static void launch_mac_v3g(rs_ctx *ctx, const MacArgs3G &a, hipStream_t st) {  // launch_mac_v3 with up to six groups
+  const size_t lds = (size_t)(2 * (4096 + 256) + 1024) * sizeof(double);
+  const unsigned rows = (unsigned)ctx->L * (unsigned)a.n_chunks;
+  const NttTable *tabs = ctx->d_coeff_tabs;
+  const unsigned parts = (unsigned)ctx->N_enc / 4096u;
+  const unsigned blocks = ((rows + 7) / 8) * 8 * parts * (unsigned)ctx->K * (unsigned)a.n_groups;
+  if (ctx->N_enc == 16384) {
+    set_max_dyn_lds((const void *)mac_kernel_v3g<false, 14>, (int)lds);
+    hipLaunchKernelGGL((mac_kernel_v3g<false, 14>), dim3(blocks), dim3(256), lds, st, a, ctx->L, ctx->K, tabs);
+  } else if (a.paired) {
+    set_max_dyn_lds((const void *)mac_kernel_v3g<true>, (int)lds);
+    hipLaunchKernelGGL(mac_kernel_v3g<true>, dim3(blocks), dim3(256), lds, st, a, ctx->L, ctx->K, tabs);
+  } else {
+    set_max_dyn_lds((const void *)mac_kernel_v3g<false>, (int)lds);
+    hipLaunchKernelGGL(mac_kernel_v3g<false>, dim3(blocks), dim3(256), lds, st, a, ctx->L, ctx->K, tabs);
+  }
+  RS_HIP(hipGetLastError());
+}
+
 static void launch_mac_v4(rs_ctx *ctx, const MacArgs4 &a, bool paired, hipStream_t st) {
   const size_t lds = (size_t)2 * (4096 + 512) * sizeof(double);  // two tiles
   const unsigned rows = (unsigned)ctx->L * (unsigned)a.n_chunks;
@@ -120,6 +143,55 @@ __global__ void __launch_bounds__(256) broadcast_rows_kernel(const uint64_t *__r
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) out[i] = vals[i / (size_t)N];
 }
+// Term tile and chunk count of one msm_run (also what rs_prove_batch_bytes sizes the workspace by).
+// wide_blocks: the call runs mac_kernel_v3g (six groups per launch) where it would run mac_kernel_v3 in pairs.
+MsmGeometry msm_geometry(const rs_ctx *ctx, int n_crs, int n_groups, size_t Tmax, size_t crs_window, bool crs_on_host, bool seeded,
+                         bool wide_blocks) {
+  const int L = ctx->L, K = ctx->K, n = ctx->N_enc;
+  const size_t enc_words = ctx->enc_words();
+  MsmGeometry G;
+  // tiling: C workspace <= ~2 GiB (knob msm_c_mib)
+  const size_t c_bytes_per_term = (size_t)n_groups * L * n * sizeof(double);
+  size_t tile_terms = std::max<size_t>(1, std::min<size_t>(Tmax, ((size_t)g_tune.msm_c_mib << 20) / c_bytes_per_term));
+  if (crs_window) {
+    size_t p2 = 1;
+    while (p2 * 2 <= tile_terms) p2 *= 2;
+    tile_terms = std::min(p2, crs_window);
+    RS_REQUIRE(crs_window % tile_terms == 0, "crs_window must be a multiple of the term tile (use a power of two)");
+  }
+  if (crs_on_host || seeded) {
+    tile_terms = std::min<size_t>(tile_terms, (size_t)std::max(1, g_tune.msm_host_tile));
+    if (crs_window) {
+      size_t p2 = 1;
+      while (p2 * 2 <= tile_terms) p2 *= 2;
+      tile_terms = std::min(p2, crs_window);  // may no longer divide the window: issue_copy splits a tile at the wrap
+    }
+    G.stage_words = tile_terms * enc_words;
+    G.land_words = seeded && crs_on_host ? tile_terms * (enc_words / 2) : 0;
+  }
+  // mac_kernel_v4 (two key vectors) runs ONE workgroup per CU: half the workgroup slots, half the chunks (measured at the
+  // configs[3] shape: 111 -> 106 ms)
+  const bool two_keys = n_crs == 2 && g_tune.mac_share_keys && g_tune.mac_variant >= 5 && (n == 8192 || n == 16384);
+  const int chunk_units = two_keys ? (g_tune.mac_chunk_units + 1) / 2 : g_tune.mac_chunk_units;
+  int n_chunks = (int)std::min<size_t>(tile_terms, (size_t)std::max(1, (chunk_units + L * K - 1) / (L * K)));
+  int step = 8;  // the (chunk, limb) rows of a launch are dealt to the 8 XCDs: a row count that is not a multiple of 8 leaves slots idle
+  while (step > 1 && (L * (step / 2)) % 8 == 0) step /= 2;  // smallest chunk-count granule with L * granule = 0 mod 8
+  if (n_chunks >= step && (size_t)((n_chunks + step - 1) / step * step) <= tile_terms) n_chunks = (n_chunks + step - 1) / step * step;
+  if (wide_blocks && !two_keys) {
+    // Six groups per launch instead of two: a third of the chunks gives a full launch the workgroup count -- the same whole
+    // waves of workgroups over the 8 XCDs -- that the two-group launch has, with three times the terms per workgroup behind
+    // one prologue.  The count is that of the call, whatever its group count (a last launch of fewer groups is a whole
+    // fraction of it), so that the workspace is affine in the batch size.  Rounded up to the granule again.
+    int third = std::max(1, (n_chunks * 2 + RS_MAC3G_GROUPS - 1) / RS_MAC3G_GROUPS);
+    if (third >= step) third = (third + step - 1) / step * step;
+    n_chunks = std::min(n_chunks, third);
+  }
+  if (Tmax == 0) n_chunks = 1;
+  G.tile_terms = tile_terms;
+  G.n_chunks = n_chunks;
+  return G;
+}
+
 // Core grouped MSM.  addends: optional per-output (n_crs * n_groups) device pointers to encoding
 // elements added to the result (pk.alpha / pk.beta of groth16.tcc:95,103).
 // crs_window != 0: every CRS vector is stored as `crs_window` consecutive elements and logical
@@ -127,19 +199,22 @@ __global__ void __launch_bounds__(256) broadcast_rows_kernel(const uint64_t *__r
 template <class M>
 static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
                           int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
-                          size_t crs_window, const MsmLin *lin, bool crs_on_host, const uint64_t *pub_seeds) {
+                          size_t crs_window, const MsmLin *lin, bool crs_on_host, const uint64_t *pub_seeds, bool wide_blocks) {
   using Lift = typename ArithOf<M>::Lift;
   constexpr bool FP = std::is_same<M, Mod>::value;
   RS_REQUIRE(n_crs >= 1 && n_crs <= 2, "n_crs must be 1 or 2");
-  RS_REQUIRE(n_groups >= 1 && n_groups <= MAX_GROUPS, "too many groups");
-  RS_REQUIRE(n_crs * n_groups <= 12, "too many outputs");
+  RS_REQUIRE(n_groups >= 1 && n_groups <= MSM_MAX_GROUPS, "too many groups");
+  // Calls of up to MAX_GROUPS groups launch what they always launched.  Beyond that -- and in the batched provers, whatever
+  // their group count -- the plaintext rows are made in blocks of MAX_GROUPS groups (PlainArgs stays inside the kernel-argument
+  // space), mac_kernel_v3 gives way to its six-group form and the reduction runs in blocks of 12 sets.
+  wide_blocks = wide_blocks || n_groups > MAX_GROUPS;
   const int L = ctx->L, K = ctx->K, n = ctx->N_enc;
   const size_t enc_words = ctx->enc_words();
   MsmState &sc = ctx->msm;
 
   // group bookkeeping
-  PlainArgs pa;
-  memset(&pa, 0, sizeof(pa));
+  std::vector<PlainGroup> groups(n_groups);
+  memset(groups.data(), 0, groups.size() * sizeof(PlainGroup));
   size_t Tmax = 0;
   std::vector<size_t> group_T(n_groups, 0);
   std::vector<unsigned *> nz_ptr(n_vecs, nullptr);
@@ -193,11 +268,10 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
       }
     RS_HIP(hipGetLastError());
   }
-  pa.ones_plain = sc.d_ones_plain;
   {
     size_t nzo = 0, ko = 0;
     for (int v = 0; v < n_vecs; v++) {
-      PlainGroup &G = pa.g[vecs[v].group];
+      PlainGroup &G = groups[vecs[v].group];
       RS_REQUIRE(G.n < MAX_GROUP_VECS, "too many vectors in one group");
       G.coeff[G.n] = coeff_ptr[v];
       G.slot_const[G.n] = (vecs[v].slot_const && sc_native) ? 1 : 0;
@@ -221,21 +295,13 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     for (int g = 0; g < n_groups; g++)
       if (lin[g].count > 0) {
         RS_REQUIRE(lin[g].T <= crs_len && !h_used, "linear-form vector: too long, or used-term counts requested");
-        pa.g[g].lin = lin[g];
+        groups[g].lin = lin[g];
         has_lin = true;
         Tmax = std::max<size_t>(Tmax, (size_t)lin[g].T);
         group_T[g] = std::max<size_t>(group_T[g], (size_t)lin[g].T);
       }
   const int n_sets = n_crs * n_groups;
-  // tiling: C workspace <= ~2 GiB (knob msm_c_mib)
   const size_t c_bytes_per_term = (size_t)n_groups * L * n * sizeof(double);
-  size_t tile_terms = std::max<size_t>(1, std::min<size_t>(Tmax, ((size_t)g_tune.msm_c_mib << 20) / c_bytes_per_term));
-  if (crs_window) {
-    size_t p2 = 1;
-    while (p2 * 2 <= tile_terms) p2 *= 2;
-    tile_terms = std::min(p2, crs_window);
-    RS_REQUIRE(crs_window % tile_terms == 0, "crs_window must be a multiple of the term tile (use a power of two)");
-  }
   // Host-resident key (crs_on_host: d_crs are HOST pointers -- a proving key larger than HBM, e.g. the 384 GiB key of the
   // 2^16-constraint headline on one GPU): the term tiles are streamed through two device staging buffers; the copy of
   // tile k+1 runs on its own stream under the kernels of tile k (pinned host memory, rs_host_alloc, for real overlap).
@@ -246,17 +312,10 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   const bool seeded = pub_seeds != nullptr, staged = crs_on_host || seeded;
   const size_t key_words = seeded ? enc_words / 2 : enc_words;  // words of a stored element
   uint64_t *stage = nullptr, *land = nullptr;
-  size_t stage_words = 0;
+  const MsmGeometry geo = msm_geometry(ctx, n_crs, n_groups, Tmax, crs_window, crs_on_host, seeded, wide_blocks);
+  const size_t tile_terms = geo.tile_terms, stage_words = geo.stage_words;
   if (staged) {
-    tile_terms = std::min<size_t>(tile_terms, (size_t)std::max(1, g_tune.msm_host_tile));
-    if (crs_window) {
-      size_t p2 = 1;
-      while (p2 * 2 <= tile_terms) p2 *= 2;
-      tile_terms = std::min(p2, crs_window);  // may no longer divide the window: issue_copy splits a tile at the wrap
-    }
-    stage_words = tile_terms * enc_words;
-    const size_t land_words = seeded && crs_on_host ? tile_terms * key_words : 0;
-    stage = (uint64_t *)ws_get(ctx, WS_SMALL, (size_t)2 * n_crs * (stage_words + land_words) * sizeof(uint64_t));
+    stage = (uint64_t *)ws_get(ctx, WS_SMALL, (size_t)2 * n_crs * (stage_words + geo.land_words) * sizeof(uint64_t));
     land = stage + (size_t)2 * n_crs * stage_words;
   }
   if (crs_on_host) {
@@ -298,17 +357,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     if (staged) return stage_at(cur_tile & 1, c);
     return d_crs[c] + (crs_window ? t0 % crs_window : t0) * enc_words;
   };
-  // mac_kernel_v4 (two key vectors) runs ONE workgroup per CU: half the workgroup slots, half the chunks (measured at the
-  // configs[3] shape: 111 -> 106 ms)
-  const int chunk_units = (n_crs == 2 && g_tune.mac_share_keys && g_tune.mac_variant >= 5 && (n == 8192 || n == 16384)) ? (g_tune.mac_chunk_units + 1) / 2
-                                                                                                              : g_tune.mac_chunk_units;
-  int n_chunks = (int)std::min<size_t>(tile_terms, (size_t)std::max(1, (chunk_units + L * K - 1) / (L * K)));
-  {  // the (chunk, limb) rows of a launch are dealt to the 8 XCDs: a row count that is not a multiple of 8 leaves slots idle
-    int step = 8;
-    while (step > 1 && (L * (step / 2)) % 8 == 0) step /= 2;  // smallest chunk-count granule with L * granule = 0 mod 8
-    if (n_chunks >= step && (size_t)((n_chunks + step - 1) / step * step) <= tile_terms) n_chunks = (n_chunks + step - 1) / step * step;
-  }
-  if (Tmax == 0) n_chunks = 1;
+  const int n_chunks = geo.n_chunks;
   Lift *d_C = (Lift *)ws_get(ctx, WS_MSM_ROWS, std::max<size_t>(256, tile_terms * c_bytes_per_term));
   uint64_t *d_partial = (uint64_t *)ws_get(ctx, WS_MSM_PARTIAL, (size_t)n_chunks * n_sets * enc_words * sizeof(uint64_t));
   const size_t lds = padded_len((size_t)n) * sizeof(double);
@@ -329,7 +378,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     uint64_t maxq = 0;
     for (int i = 0; i < L; i++) maxq = std::max(maxq, ctx->q[i]);
     int max_vecs = 1;
-    for (int g = 0; g < n_groups; g++) max_vecs = std::max(max_vecs, pa.g[g].n);
+    for (int g = 0; g < n_groups; g++) max_vecs = std::max(max_vecs, groups[g].n);
     hybrid = ctx->hybrid && g_tune.mac_variant >= 5 && (n == 8192 || n == 16384) &&
              (double)max_vecs * (0.5 * (double)maxq + 1.0) < 9007199254740992.0;
     v3 = hybrid;
@@ -337,7 +386,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   RS_REQUIRE(!has_lin || plain_wide, "linear-form vectors need the wide plaintext kernel");
   const bool paired = v3 && plain_wide;  // row layout of this call: written by the plaintext kernel, read by the MAC
   bool multi = false;
-  for (int g = 0; g < n_groups; g++) multi = multi || pa.g[g].n > 1;
+  for (int g = 0; g < n_groups; g++) multi = multi || groups[g].n > 1;
   if (plain16)
     set_max_dyn_lds((const void *)plain_center_kernel<16, 0, M>, (int)lds);
   else
@@ -364,13 +413,21 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
                           stage_at(tile_idx & 1, c), st);
     double rows_in = 0;  // coefficient rows (term, limb) read by this tile
     for (int v = 0; v < n_vecs; v++) rows_in += (double)(vecs[v].T > t0 ? std::min(tt, vecs[v].T - t0) : 0) * L;
-    {
-    ProfScope prof_plain(ctx, st, plain_wide ? "plain_center_wide_kernel" : "plain_center_kernel", rows_in * (double)ctx->N * 8.0 + (double)tt * L * n_groups * nd * 8.0,
-                         rows_in * (ntt_fp64(nd, logn_d) + 14.0 * nd));
+    // plaintext rows, MAX_GROUPS groups per launch (one launch for the calls of up to MAX_GROUPS groups)
+    for (int pg0 = 0; pg0 < n_groups; pg0 += MAX_GROUPS) {
+    const int png = std::min(MAX_GROUPS, n_groups - pg0);
+    PlainArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    for (int g = 0; g < png; g++) pa.g[g] = groups[pg0 + g];
+    pa.ones_plain = sc.d_ones_plain;
+    Lift *const d_Cb = d_C + (size_t)pg0 * tile_terms * L * n;  // rows of the block's first group
+    const double rows_blk = png == n_groups ? rows_in : rows_in * (double)png / (double)n_groups;  // profile figure
+    ProfScope prof_plain(ctx, st, plain_wide ? "plain_center_wide_kernel" : "plain_center_kernel", rows_blk * (double)ctx->N * 8.0 + (double)tt * L * png * nd * 8.0,
+                         rows_blk * (ntt_fp64(nd, logn_d) + 14.0 * nd));
     if (plain_wide) {
       if constexpr (FP) {
         const int wl = (int)WideShape<13>::LDS_BYTES;
-        const unsigned long long items = (unsigned long long)tt * n_groups;
+        const unsigned long long items = (unsigned long long)tt * png;
         const unsigned slots = (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>(items, (512 + L - 1) / L));
         const dim3 grid(slots * (unsigned)L);
         PlainTwPtrs twp;
@@ -381,8 +438,8 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     set_max_dyn_lds((const void *)plain_center_wide_kernel<MULTI_, PAIRED_, NE_, LIN_>, \
                                wl);                                              \
     hipLaunchKernelGGL((plain_center_wide_kernel<MULTI_, PAIRED_, NE_, LIN_>), grid, dim3(256), wl, st, pa,                   \
-                       reinterpret_cast<double *>(d_C), (unsigned long long)t0, (unsigned long long)tile_terms,               \
-                       (unsigned long long)tt, n_groups, ctx->N, L, ctx->d_index_map, ctx->d_plain_tabs, twp);                  \
+                       reinterpret_cast<double *>(d_Cb), (unsigned long long)t0, (unsigned long long)tile_terms,              \
+                       (unsigned long long)tt, png, ctx->N, L, ctx->d_index_map, ctx->d_plain_tabs, twp);                       \
   } while (0)
 #define RS_PLAIN_WIDE(MULTI_, PAIRED_)                                  \
   do {                                                                  \
@@ -402,11 +459,11 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
 #undef RS_PLAIN_WIDE
       }
     } else if (plain16)
-      hipLaunchKernelGGL((plain_center_kernel<16, 0, M>), dim3((unsigned)tt, L, n_groups), dim3(plain_thr), lds, st, pa, d_C,
+      hipLaunchKernelGGL((plain_center_kernel<16, 0, M>), dim3((unsigned)tt, L, png), dim3(plain_thr), lds, st, pa, d_Cb,
                          (unsigned long long)t0, (unsigned long long)tile_terms, ctx->N, L, ctx->logN_enc,
                          ctx->d_index_map, CtxArith<M>::d_plain(ctx), hybrid ? 1 : 0);
     else
-      hipLaunchKernelGGL((plain_center_kernel<8, 0, M>), dim3((unsigned)tt, L, n_groups), dim3(thr), lds, st, pa, d_C,
+      hipLaunchKernelGGL((plain_center_kernel<8, 0, M>), dim3((unsigned)tt, L, png), dim3(thr), lds, st, pa, d_Cb,
                          (unsigned long long)t0, (unsigned long long)tile_terms, ctx->N, L, ctx->logN_enc,
                          ctx->d_index_map, CtxArith<M>::d_plain(ctx), hybrid ? 1 : 0);
     }
@@ -493,6 +550,42 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
                            terms * L * K * (ntt_fp64(nd, logn_d) + 8.0 * nd / 2.0 + 2.0 * 15.0 * nd));
             launch_mac_v4(ctx, a4, paired, st);
           }
+        } else if (wide_blocks) {
+          // mac_kernel_v3g: up to six groups share the ciphertext words of a launch (chunk count: msm_geometry)
+          for (int c = 0; c < n_crs; c++)
+            for (int g0 = 0; g0 < n_groups; g0 += RS_MAC3G_GROUPS) {
+              const int ng = std::min(RS_MAC3G_GROUPS, n_groups - g0);
+              MacArgs3G a3;
+              memset(&a3, 0, sizeof(a3));
+              unsigned long long tmax = 0;
+              double terms = 0;
+              for (int gi = 0; gi < ng; gi++) {
+                a3.C[gi] = reinterpret_cast<const double *>(Cptr(g0 + gi));
+                a3.terms[gi] = group_terms(g0 + gi);
+                a3.partial[gi] = d_partial + (size_t)(c * n_groups + g0 + gi) * enc_words;
+                tmax = std::max(tmax, a3.terms[gi]);
+                terms += (double)a3.terms[gi];
+              }
+              a3.crs = crs_at(c, t0);
+              a3.part_stride = (size_t)n_sets * enc_words;
+              a3.n_groups = ng;
+              a3.paired = paired;
+              a3.ct_temporal = g_tune.mac_ct_temporal;
+              a3.n_chunks = base.n_chunks;
+              a3.terms_per_chunk = base.terms_per_chunk;
+              a3.accumulate = base.accumulate;
+              a3.acc_period = base.acc_period;
+              a3.reduce_u = 0;
+              for (int jj = 0; jj < K; jj++) {
+                double end = 0;
+                a3.red_mask[jj] = fwd_reduce_mask_from(ctx->Q[jj], ctx->logN_enc, b0, &end);
+                if (end > 562949953421312.0) a3.reduce_u = 1;
+              }
+              // ciphertext words once per launch (the other groups' reads are served on-die), every plaintext row once
+              ProfScope prof(ctx, st, n == 16384 ? "mac_kernel_v3g<false, 14>" : "mac_kernel_v3g", (double)tmax * (double)enc_words * 8.0 + terms * (double)L * nd * 8.0 + ng * (double)enc_words * 8.0,
+                             terms * L * K * (ntt_fp64(nd, logn_d) + 8.0 * nd / 2.0 + 15.0 * nd));
+              launch_mac_v3g(ctx, a3, st);
+            }
         } else
         // chunks: two workgroups per CU in one wave of workgroups (512), shared by the groups of a launch
         for (int c = 0; c < n_crs; c++)
@@ -578,11 +671,23 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
     }
     if (crs_on_host) RS_HIP(hipEventRecord(sc.ev_freed[tile_idx & 1], st));  // its readers are enqueued: the buffer may be refilled after them
   }
-  ReduceArgs ra;
-  memset(&ra, 0, sizeof(ra));
-  if (addends)
-    for (int s_ = 0; s_ < n_sets; s_++) ra.addend[s_] = addends[s_];
-  {
+  for (int s0 = 0; n_sets > 12 && s0 < n_sets; s0 += 12) {  // more sets than ReduceArgs holds: blocks of 12
+    const int ns = std::min(12, n_sets - s0);
+    ReduceArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    if (addends)
+      for (int s_ = 0; s_ < ns; s_++) ra.addend[s_] = addends[s0 + s_];
+    const size_t total = (size_t)ns * enc_words;
+    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(reduce_block_kernel, dim3(blocks), dim3(256), 0, st, d_partial, d_out, ra, n_chunks, s0, ns, n_sets, enc_words, n,
+                       K, ctx->d_Qint);
+    RS_HIP(hipGetLastError());
+  }
+  if (n_sets <= 12) {
+    ReduceArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    if (addends)
+      for (int s_ = 0; s_ < n_sets; s_++) ra.addend[s_] = addends[s_];
     const size_t total = (size_t)n_sets * enc_words;
     const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 16);
     hipLaunchKernelGGL(reduce_kernel, dim3(blocks), dim3(256), 0, st, d_partial, d_out, ra, n_chunks, n_sets, enc_words, n,
@@ -605,9 +710,9 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
 
 void msm_run(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
              int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
-             size_t crs_window, const MsmLin *lin, bool crs_on_host, const uint64_t *pub_seeds) {
-  RS_DISPATCH_ARITH(ctx, (msm_run_arith<Mod>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host, pub_seeds)),
-                    (msm_run_arith<ModI>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host, pub_seeds)));
+             size_t crs_window, const MsmLin *lin, bool crs_on_host, const uint64_t *pub_seeds, bool wide_blocks) {
+  RS_DISPATCH_ARITH(ctx, (msm_run_arith<Mod>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host, pub_seeds, wide_blocks)),
+                    (msm_run_arith<ModI>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host, pub_seeds, wide_blocks)));
 }
 // can a call with linear-form vectors be served? (FP64 context on the wide plaintext kernel)
 bool msm_supports_lin(const rs_ctx *ctx) {

@@ -5,7 +5,7 @@
 // in prover.hip.
 #include <algorithm>
 
-#include "../../include/ringsnark_amd/seeded.h"
+#include "../../include/ringsnark_amd/batch.h"
 #include "rs_internal.hpp"
 
 namespace rs {
@@ -146,6 +146,28 @@ int rs_rinocchio_prove_seeded(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio
   const rs_rinocchio_pk full{pk->s_pows, pk->alpha_s_pows, pk->beta_prods, pk->d_beta_rv_ts, pk->d_beta_rw_ts, pk->d_beta_ry_ts,
                              pk->window, pk->host_key};
   rinocchio_prove_run(ctx, cs, &full, pk->pub_seeds, d_assignment, h_assignment_kinds, d_d1, d_d2, d_d3, d_proof, h_empty, S(stream));
+  RS_API_END
+}
+
+int rs_groth16_prove_batch_seeded(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk_seeded *pk, int batch,
+                                  const uint64_t *const *d_assignments, const uint8_t *h_assignment_kinds, uint64_t *d_proofs,
+                                  int *h_empty, rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  RS_REQUIRE(pk != nullptr, "null argument");
+  const rs_groth16_pk full{pk->s_pows, pk->delta_ts, pk->delta_mid, pk->d_alpha, pk->d_beta, pk->window, pk->host_key};
+  groth16_prove_batch_run(ctx, cs, &full, pk->pub_seeds, batch, d_assignments, h_assignment_kinds, d_proofs, h_empty, S(stream));
+  RS_API_END
+}
+
+int rs_rinocchio_prove_batch_seeded(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk_seeded *pk, int batch,
+                                    const uint64_t *const *d_assignments, const uint8_t *h_assignment_kinds, const uint64_t *d_d123,
+                                    uint64_t *d_proofs, int *h_empty, rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  RS_REQUIRE(pk != nullptr, "null argument");
+  const rs_rinocchio_pk full{pk->s_pows, pk->alpha_s_pows, pk->beta_prods, pk->d_beta_rv_ts, pk->d_beta_rw_ts, pk->d_beta_ry_ts,
+                             pk->window, pk->host_key};
+  rinocchio_prove_batch_run(ctx, cs, &full, pk->pub_seeds, batch, d_assignments, h_assignment_kinds, d_d123, d_proofs, h_empty,
+                            S(stream));
   RS_API_END
 }
 

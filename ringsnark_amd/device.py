@@ -699,6 +699,81 @@ class Device:
         _lib.check(prove(self.h, dcs.h, C.byref(s), _ptr(assignment), kp, _ptr(d1), _ptr(d2), _ptr(d3), _ptr(proof), empty, self.stream()))
         return proof, [int(e) for e in empty]
 
+    # ---- batched proving (include/ringsnark_amd/batch.h)
+    def _groth16_key(self, pk, window):
+        """(key struct, seeded) of a key dictionary, dispatched as groth16_prove does"""
+        host_key = isinstance(pk["s_pows"], HostWords)
+        addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
+        assert all(isinstance(pk[k], HostWords) == host_key for k in ("s_pows", "delta_ts") + (("delta_mid",) if pk.get("delta_mid") is not None else ()))
+        if "pub_seeds" in pk:
+            return _lib.Groth16PKSeeded(addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk.get("delta_mid")),
+                                        (C.c_uint64 * 3)(*self._keygen_seeds(list(pk["pub_seeds"][:3]), 3)), pk["alpha"].data_ptr(),
+                                        pk["beta"].data_ptr(), window, 1 if host_key else 0), True
+        return _lib.Groth16PK(addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk.get("delta_mid")), pk["alpha"].data_ptr(),
+                              pk["beta"].data_ptr(), window, 1 if host_key else 0), False
+
+    def _rinocchio_key(self, pk, window):
+        host_key = isinstance(pk.get("s_pows"), HostWords)
+        g = lambda k: None if pk.get(k) is None else (pk[k].ptr if isinstance(pk[k], HostWords) else pk[k].data_ptr())
+        if "pub_seeds" in pk:
+            return _lib.RinocchioPKSeeded(g("s_pows"), g("alpha_s_pows"), g("beta_prods"),
+                                          (C.c_uint64 * 3)(*self._keygen_seeds(list(pk["pub_seeds"][:3]), 3)), g("beta_rv_ts"),
+                                          g("beta_rw_ts"), g("beta_ry_ts"), window, 1 if host_key else 0), True
+        return _lib.RinocchioPK(g("s_pows"), g("alpha_s_pows"), g("beta_prods"), g("beta_rv_ts"), g("beta_rw_ts"), g("beta_ry_ts"),
+                                window, 1 if host_key else 0), False
+
+    def _batch_args(self, dcs, assignments, kinds, check):
+        """(B, host array of the members' device pointers, kinds array [B][n_vars] or None and its pointer)"""
+        assignments = list(assignments)
+        B = len(assignments)
+        if check:
+            for b, a in enumerate(assignments):
+                try:
+                    self._require_satisfied(dcs, a)
+                except ValueError as e:
+                    raise ValueError("batch member %d: %s" % (b, e)) from None
+        ptrs = (C.c_void_p * max(B, 1))(*[a.data_ptr() for a in assignments])
+        if kinds is None:
+            return B, ptrs, None, None
+        k = np.ascontiguousarray(np.stack([np.zeros(dcs.n_vars, dtype=np.uint8) if x is None else np.asarray(x, dtype=np.uint8)
+                                           for x in kinds]))
+        assert k.shape == (B, dcs.n_vars), (k.shape, B, dcs.n_vars)
+        return B, ptrs, k, k.ctypes.data_as(_lib.u8p)
+
+    def groth16_prove_batch(self, dcs, pk, assignments, window=0, kinds=None, check=False):
+        """Proves the B assignments (a list of device tensors [n_vars][L][N], 1 <= B <= 8) of one system against one key in one
+        pass over every key vector (rs_groth16_prove_batch): a tile of a host-resident or seeded key is copied / expanded once
+        per batch.  pk, window as in groth16_prove (HostWords: a host key; "pub_seeds": a seeded key).  kinds: None, or one
+        entry per member, each None or [n_vars] RS_KIND_*.  check: r1cs_check on every member first; ValueError naming the
+        member and its first violated constraint, before anything is proved.
+        Returns (proofs [B][3] encoding elements, empties [B][3]); member b's are what groth16_prove returns for it."""
+        B, ptrs, keep, kp = self._batch_args(dcs, assignments, kinds, check)
+        s, seeded = self._groth16_key(pk, window)
+        proofs = self.enc_empty(max(B, 1), 3)
+        empty = (C.c_int * (3 * max(B, 1)))()
+        prove = self.lib.rs_groth16_prove_batch_seeded if seeded else self.lib.rs_groth16_prove_batch
+        _lib.check(prove(self.h, dcs.h, C.byref(s), B, ptrs, kp, _ptr(proofs), empty, self.stream()))
+        return proofs, [[int(empty[3 * b + k]) for k in range(3)] for b in range(B)]
+
+    def rinocchio_prove_batch(self, dcs, pk, assignments, d=None, window=0, kinds=None, check=False):
+        """As groth16_prove_batch (rs_rinocchio_prove_batch).  d: None (non-ZK) or a device tensor [B][3][L][N], the ring
+        elements d1, d2, d3 of every member.  Returns (proofs [B][9], empties [B][9])."""
+        B, ptrs, keep, kp = self._batch_args(dcs, assignments, kinds, check)
+        if d is not None:
+            assert self._count(d, self.ring_words) == 3 * B, "d holds d1, d2, d3 of every member"
+        s, seeded = self._rinocchio_key(pk, window)
+        proofs = self.enc_empty(max(B, 1), 9)
+        empty = (C.c_int * (9 * max(B, 1)))()
+        prove = self.lib.rs_rinocchio_prove_batch_seeded if seeded else self.lib.rs_rinocchio_prove_batch
+        _lib.check(prove(self.h, dcs.h, C.byref(s), B, ptrs, kp, _ptr(d), _ptr(proofs), empty, self.stream()))
+        return proofs, [[int(empty[9 * b + k]) for k in range(9)] for b in range(B)]
+
+    def prove_batch_bytes(self, dcs, scheme, batch):
+        """Bytes of context workspace a batched proof of `batch` members holds (rs_prove_batch_bytes); scheme "groth16" | "rinocchio"."""
+        n = C.c_size_t(0)
+        _lib.check(self.lib.rs_prove_batch_bytes(self.h, dcs.h, {"groth16": 0, "rinocchio": 1}[scheme], batch, C.byref(n)))
+        return n.value
+
     # ---- measurement / synthetic workloads
     def set_profiling(self, on):
         _lib.check(self.lib.rs_set_profiling(self.h, 1 if on else 0))
