@@ -15,6 +15,7 @@ RS_OK, RS_ERR_INVALID, RS_ERR_HIP, RS_ERR_UNSUPPORTED, RS_ERR_NOT_INVERTIBLE, RS
 RS_MOD_PLAIN, RS_MOD_COEFF = 0, 1
 RS_KIND_POLY, RS_KIND_ONE = 0, 2
 RS_EVAL_FULL, RS_EVAL_IO, RS_EVAL_MID = 0, 1, 2
+RS_SOLVE_AUTO, RS_SOLVE_LEVELS, RS_SOLVE_WALK = 0, 1, 2
 
 u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
@@ -54,6 +55,16 @@ class Peaks(C.Structure):
 class R1csReport(C.Structure):
     _fields_ = [("n_violated", C.c_uint64), ("first_row", C.c_uint64), ("first_limb", C.c_uint32), ("first_slot", C.c_uint32),
                 ("a", C.c_uint64), ("b", C.c_uint64), ("c", C.c_uint64)]
+
+
+class SolveInfo(C.Structure):
+    _fields_ = [("n_given", C.c_uint64), ("n_solved", C.c_uint64), ("n_unsolved", C.c_uint64), ("first_unsolved", C.c_uint64),
+                ("n_levels", C.c_uint64), ("max_width", C.c_uint64), ("n_unused", C.c_uint64), ("first_blocked", C.c_uint64),
+                ("blocked_reason", C.c_uint32)]
+
+
+class SolveStats(C.Structure):
+    _fields_ = [("level_launches", C.c_uint32), ("walk_launches", C.c_uint32)]
 
 
 class VerifyReport(C.Structure):
@@ -169,6 +180,13 @@ CHECK_SIGNATURES = {  # every function of include/ringsnark_amd/r1cs_check.h
     "rs_r1cs_check": (C.c_int, [vp, vp, vp, vp, C.POINTER(R1csReport), vp]),
 }
 
+SOLVE_SIGNATURES = {  # every function of include/ringsnark_amd/r1cs_solve.h
+    "rs_r1cs_solve_plan_create": (C.c_int, [vp, vp, u8p, C.POINTER(vp), C.POINTER(SolveInfo)]),
+    "rs_r1cs_solve_plan_steps": (C.c_int, [vp, u32p, u32p, u64p]),
+    "rs_r1cs_solve_plan_destroy": (None, [vp]),
+    "rs_r1cs_solve": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(SolveStats), vp]),
+}
+
 VERIFY_SIGNATURES = {  # every function of include/ringsnark_amd/verify.h
     "rs_io_eval_at": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "rs_groth16_vk_create": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
@@ -217,8 +235,8 @@ def load():
             "ringsnark_amd/librs_hip.so is not built (run `python -c 'import __graft_entry__ as g; g.build()'`); "
             "the HIP library is the only implementation, there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **VERIFY_SIGNATURES, **KEYGEN_SIGNATURES,
-                              **SEEDED_SIGNATURES, **BATCH_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **SOLVE_SIGNATURES, **VERIFY_SIGNATURES,
+                              **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -23,17 +23,7 @@ constexpr int CHECK_R = 2;
 // device side of the report: [0] key of the first violation (all ones: none), [1] violated rows, [2..4] a, b, c there
 constexpr int CHECK_WORDS = 5;
 
-// Workgroup `w` of `n` -> the position it takes in the (slot chunk, row group) order.  Blocks are dealt round-robin over the
-// eight XCDs (b and b + 8 share one), so the blocks of one XCD get a contiguous run of positions: one slot chunk, neighbouring
-// row groups -- rows of real circuits share variables with their neighbours, and the second reader of a wire then finds it
-// in that XCD's L2 (measured: 7 % on wide_r1cs at 2^13 constraints, nothing on the chain, whose rows share wires inside a
-// group).  Bijective for every n (the plain (w % 8) * ceil(n / 8) + w / 8 is not when n % 8 != 0).  Placement changes speed only.
-__device__ __forceinline__ unsigned xcd_position(unsigned w, unsigned n) {
-  const unsigned q = n >> 3, r = n & 7u, x = w & 7u;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (w >> 3);
-}
-
-// grid: (slot chunks of 256 slot pairs) x (row groups of `rpw` rows), one dimension, ordered by xcd_position.
+// grid: (slot chunks of 256 slot pairs) x (row groups of `rpw` rows), one dimension, ordered by xcd_position (witness_eval.hpp).
 // A thread owns one slot pair (16-byte loads of the assignment) and walks the rows of its group CHECK_R at a time.
 template <class M>
 __global__ void __launch_bounds__(256)

@@ -1,0 +1,425 @@
+// r1cs_solve.hip -- the assignment solver (include/ringsnark_amd/r1cs_solve.h): the full assignment [n_vars][L][N] of a
+// forward-determined R1CS from its given wires, the step before rs_r1cs_check and the provers.
+//
+// A ring element in evaluation form is L*N independent residues, so solving the system is L*N independent scalar problems
+// with ONE schedule.  The schedule is built on the host (build_schedule: unknown-counters per constraint and a wire ->
+// constraint adjacency, O(nnz) apart from sorting each level's candidates); two kernels run it:
+//   solve_level_kernel  one level per launch, grid (slot chunks x groups of steps): the steps of a level are independent, the
+//                       levels are ordered by the stream
+//   solve_walk_kernel   a run of consecutive levels per launch, grid slot chunks only: every thread walks the run's steps in
+//                       order for its own slot pair and only ever re-reads words it stored itself (chain_kernel of
+//                       prover.hip with the schedule read from memory)
+// No kernel waits on another workgroup.  Every index into the assignment comes from the plan and the CSR, both validated
+// on the host; none is computed from assignment data.
+#include <algorithm>
+
+#include "../../include/ringsnark_amd/r1cs_solve.h"
+#include "witness_eval.hpp"
+
+namespace rs {
+
+// RS_SOLVE_AUTO: a level goes to the level kernel when its launch fills the device, width x slot chunks >= one workgroup
+// per CU (256 CUs); consecutive narrower levels are merged into one walk launch.  A starting rule derived from the CU
+// count, not a measured optimum (DESIGN.md "Assignment solver").
+constexpr size_t SOLVE_FILL_WORKGROUPS = 256;
+// steps per workgroup of the level kernel: as many as leave the device a few waves of workgroups (as CHECK's rows per workgroup)
+constexpr size_t SOLVE_STEPS_PER_WG = 8;
+
+// the three matrices as the kernels read them
+template <class T>
+struct SolveCsr {
+  const uint32_t *rp[3], *col[3];
+  const T *cf[3];  // [L][nnz]
+  size_t nnz[3];
+  const int32_t *px[3];
+  const T *ptab;
+};
+
+// bounds of the three rows of one step, its target and k^-1: everything of a step that does not depend on the assignment
+template <class T>
+struct SolveStep {
+  uint32_t e0[3], e1[3], wire;
+  T kinv;
+};
+template <class T>
+__device__ __forceinline__ SolveStep<T> load_step(const SolveCsr<T> &cs, const uint32_t *__restrict__ step_row,
+                                                  const uint32_t *__restrict__ step_wire, const T *__restrict__ kinv_limb, size_t s) {
+  SolveStep<T> st;
+  const uint32_t row = step_row[s];
+#pragma unroll
+  for (int w = 0; w < 3; w++) {
+    st.e0[w] = cs.rp[w][row];
+    st.e1[w] = cs.rp[w][row + 1];
+  }
+  st.wire = step_wire[s];
+  st.kinv = kinv_limb[s];
+  return st;
+}
+
+// target = (<a,z> * <b,z> - <c,z> without the target) * k^-1 for one slot pair, stored as canonical residues
+template <class M>
+__device__ __forceinline__ void solve_step(const SolveCsr<typename ArithOf<M>::T> &cs, const SolveStep<typename ArithOf<M>::T> &st,
+                                           uint64_t *asg, size_t S, size_t pair, int limb, const M mod) {
+  using T = typename ArithOf<M>::T;
+  T a0, a1, b0, b1, c0, c1;
+  eval_row_pair_skip<M>(cs.col[0], cs.cf[0] + (size_t)limb * cs.nnz[0], st.e0[0], st.e1[0], asg, S, pair, ~0u, mod, a0, a1, cs.px[0], cs.ptab);
+  eval_row_pair_skip<M>(cs.col[1], cs.cf[1] + (size_t)limb * cs.nnz[1], st.e0[1], st.e1[1], asg, S, pair, ~0u, mod, b0, b1, cs.px[1], cs.ptab);
+  eval_row_pair_skip<M>(cs.col[2], cs.cf[2] + (size_t)limb * cs.nnz[2], st.e0[2], st.e1[2], asg, S, pair, st.wire + 1, mod, c0, c1, cs.px[2], cs.ptab);
+  // two canonical residues, one operand centred (the dyadic product of rs_core.hip); the difference is reduced before it
+  // meets the constant: |product| <= 0.75 p and c < p leave 1.75 p, beyond what mulmod takes beside |k^-1| <= p / 2 at 50 bits
+  const T d0 = reduce(subm(mulmod_dd(a0, center(b0, mod), mod), c0, mod), mod);
+  const T d1 = reduce(subm(mulmod_dd(a1, center(b1, mod), mod), c1, mod), mod);
+  ulonglong2 o;
+  o.x = to_res(canon(mulmod(d0, st.kinv, mod), mod));
+  o.y = to_res(canon(mulmod(d1, st.kinv, mod), mod));
+  reinterpret_cast<ulonglong2 *>(asg + (size_t)st.wire * S)[pair] = o;
+}
+
+// grid: (slot chunks of 256 slot pairs) x (groups of `spw` steps of the level [s_lo, s_hi)), one dimension, ordered by
+// xcd_position.  A thread owns one slot pair.  The rows read (levels below) and the rows written (this level) are disjoint.
+template <class M>
+__global__ void __launch_bounds__(256)
+solve_level_kernel(const SolveCsr<typename ArithOf<M>::T> cs, const uint32_t *__restrict__ step_row, const uint32_t *__restrict__ step_wire,
+                   const typename ArithOf<M>::T *__restrict__ kinv /* [L][n_steps] */, size_t n_steps, size_t s_lo, size_t s_hi,
+                   uint64_t *asg, int N, int L, const M *__restrict__ qmod, unsigned n_groups, unsigned spw) {
+  const unsigned pos = xcd_position(blockIdx.x, gridDim.x);
+  const unsigned chunk = pos / n_groups, group = pos % n_groups;
+  const size_t S = (size_t)L * N;
+  const size_t pair = (size_t)chunk * 256 + threadIdx.x;
+  if (2 * pair >= S) return;
+  const int limb = (int)((2 * pair) / (size_t)N);
+  const M mod = qmod[limb];
+  const size_t lo = s_lo + (size_t)group * spw, hi = lo + spw < s_hi ? lo + spw : s_hi;
+  for (size_t s = lo; s < hi; s++) solve_step<M>(cs, load_step(cs, step_row, step_wire, kinv + (size_t)limb * n_steps, s), asg, S, pair, limb, mod);
+}
+
+// grid: slot chunks.  Every thread walks the steps [s_lo, s_hi) in order for its own slot pair: what a step reads was given
+// or was stored by this very thread in an earlier step, so program order is all the ordering there is -- `asg` is neither
+// const nor restrict, and its loads are ordinary vector loads behind the thread's own stores.  The words of step s + 1 that
+// do not depend on the assignment (schedule, row bounds, k^-1: wave-uniform) are loaded while step s computes; only the
+// assignment loads sit on the dependent chain.
+template <class M>
+__global__ void __launch_bounds__(256)
+solve_walk_kernel(const SolveCsr<typename ArithOf<M>::T> cs, const uint32_t *__restrict__ step_row, const uint32_t *__restrict__ step_wire,
+                  const typename ArithOf<M>::T *__restrict__ kinv /* [L][n_steps] */, size_t n_steps, size_t s_lo, size_t s_hi,
+                  uint64_t *asg, int N, int L, const M *__restrict__ qmod) {
+  using T = typename ArithOf<M>::T;
+  const size_t S = (size_t)L * N;
+  const size_t pair = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (2 * pair >= S || s_lo >= s_hi) return;
+  const int limb = (int)((2 * pair) / (size_t)N);
+  const M mod = qmod[limb];
+  const T *kinv_limb = kinv + (size_t)limb * n_steps;
+  SolveStep<T> next = load_step(cs, step_row, step_wire, kinv_limb, s_lo);
+  for (size_t s = s_lo; s < s_hi; s++) {
+    const SolveStep<T> cur = next;
+    if (s + 1 < s_hi) next = load_step(cs, step_row, step_wire, kinv_limb, s + 1);
+    solve_step<M>(cs, cur, asg, S, pair, limb, mod);
+  }
+}
+
+// one kernel launch of a solve: kind 0 = the level kernel on one level, 1 = the walk kernel on a run of levels
+struct SolveLaunch {
+  int kind;
+  size_t s_lo, s_hi;
+  double bytes, ops;  // ProfScope: algorithmic bytes and FP64 instructions per lane
+};
+
+}  // namespace rs
+
+struct rs_r1cs_solve_plan {
+  rs_ctx *ctx = nullptr;
+  const rs_r1cs *cs = nullptr;
+  rs_r1cs_solve_info info{};
+  std::vector<uint32_t> rows, wires;  // the steps, ordered by (level, constraint)
+  std::vector<uint64_t> level_ptr;    // [n_levels + 1]
+  std::vector<rs::SolveLaunch> launches[3];  // by mode
+  uint32_t *d_rows = nullptr, *d_wires = nullptr;
+  uint64_t *d_kinv = nullptr;  // [L][n_steps] constants of the context's arithmetic
+};
+
+namespace rs {
+
+// The schedule of r1cs_solve.h.  k: the coefficient sum of every step, [n_steps][L] canonical.
+static void build_schedule(const rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *h_given, rs_r1cs_solve_plan *P, std::vector<uint64_t> &k) {
+  const size_t m = cs->m, nv = cs->n_vars;
+  const int L = ctx->L;
+  RS_REQUIRE(m < ((size_t)1 << 31) && nv < 0xFFFFFFFFull, "constraint system too large for the solver");
+  std::vector<uint8_t> known(nv);
+  rs_r1cs_solve_info &info = P->info;
+  info = rs_r1cs_solve_info{};
+  for (size_t v = 0; v < nv; v++) info.n_given += (known[v] = h_given[v] ? 1 : 0);
+  // distinct unknown wires per constraint, of a and b together and of c: counters, and the wire -> constraint adjacency
+  // (entry 2 j + 1: the wire is in c of constraint j; 2 j: in a or b)
+  std::vector<uint32_t> cnt_ab(m, 0), cnt_c(m, 0), c_ptr(m + 1, 0), c_list, adj_ptr(nv + 1, 0), adj;
+  {
+    std::vector<uint32_t> seen_ab(nv, ~0u), seen_c(nv, ~0u);
+    std::vector<std::pair<uint32_t, uint32_t>> occ;  // (wire, adjacency entry)
+    for (size_t j = 0; j < m; j++) {
+      for (int w = 0; w < 3; w++)
+        for (uint32_t e = cs->h_row_ptr[w][j]; e < cs->h_row_ptr[w][j + 1]; e++) {
+          const uint32_t c = cs->h_col[w][e];
+          if (c == 0 || known[c - 1]) continue;
+          std::vector<uint32_t> &seen = w == 2 ? seen_c : seen_ab;
+          if (seen[c - 1] == (uint32_t)j) continue;
+          seen[c - 1] = (uint32_t)j;
+          (w == 2 ? cnt_c : cnt_ab)[j]++;
+          if (w == 2) c_list.push_back(c - 1);
+          occ.emplace_back(c - 1, (uint32_t)(2 * j + (w == 2)));
+          adj_ptr[c]++;
+        }
+      c_ptr[j + 1] = (uint32_t)c_list.size();
+    }
+    for (size_t v = 0; v < nv; v++) adj_ptr[v + 1] += adj_ptr[v];
+    adj.resize(occ.size());
+    std::vector<uint32_t> fill(adj_ptr.begin(), adj_ptr.end() - 1);
+    for (const auto &o : occ) adj[fill[o.first]++] = o.second;
+  }
+  auto candidate = [&](size_t j) { return cnt_ab[j] == 0 && cnt_c[j] == 1; };
+  std::vector<uint32_t> cand, next, fresh, claimed(nv, 0);
+  std::vector<uint8_t> is_step(m, 0);
+  std::vector<uint64_t> ksum(L);
+  for (size_t j = 0; j < m; j++)
+    if (candidate(j)) cand.push_back((uint32_t)j);
+  P->rows.clear();
+  P->wires.clear();
+  P->level_ptr.assign(1, 0);
+  k.clear();
+  for (uint32_t level = 1; !cand.empty(); level++) {
+    std::sort(cand.begin(), cand.end());  // a constraint becomes a candidate once: no duplicates
+    fresh.clear();
+    for (const uint32_t j : cand) {
+      if (!candidate(j)) continue;  // its last unknown was determined in the level that made it a candidate
+      uint32_t t = ~0u;
+      for (uint32_t i = c_ptr[j]; i < c_ptr[j + 1]; i++)
+        if (!known[c_list[i]]) t = c_list[i];
+      if (claimed[t] == level) continue;  // a lower constraint of this level determines it
+      bool poly = false;
+      std::fill(ksum.begin(), ksum.end(), 0);
+      const size_t z = cs->nnz[2];
+      for (uint32_t e = cs->h_row_ptr[2][j]; e < cs->h_row_ptr[2][j + 1]; e++) {
+        if (cs->h_col[2][e] != t + 1) continue;
+        if (!cs->h_pidx[2].empty() && cs->h_pidx[2][e] >= 0) poly = true;
+        for (int l = 0; l < L; l++) ksum[l] = host::addmod(ksum[l], cs->h_coeff[2][(size_t)l * z + e], ctx->q[l]);
+      }
+      if (poly || std::find(ksum.begin(), ksum.end(), 0) != ksum.end()) continue;  // never ready as things stand
+      claimed[t] = level;
+      is_step[j] = 1;
+      P->rows.push_back(j);
+      P->wires.push_back(t);
+      k.insert(k.end(), ksum.begin(), ksum.end());
+      fresh.push_back(t);
+    }
+    if (fresh.empty()) break;
+    P->level_ptr.push_back(P->rows.size());
+    info.max_width = std::max<uint64_t>(info.max_width, fresh.size());
+    next.clear();
+    for (const uint32_t t : fresh) known[t] = 1;
+    for (const uint32_t t : fresh)
+      for (uint32_t i = adj_ptr[t]; i < adj_ptr[t + 1]; i++) {
+        const uint32_t j = adj[i] >> 1;
+        (adj[i] & 1u ? cnt_c : cnt_ab)[j]--;
+        if (candidate(j)) next.push_back(j);
+      }
+    cand.swap(next);
+  }
+  info.n_solved = P->rows.size();
+  info.n_unsolved = nv - info.n_given - info.n_solved;
+  info.n_levels = P->level_ptr.size() - 1;
+  info.n_unused = m - info.n_solved;
+  info.first_unsolved = nv;
+  for (size_t v = 0; v < nv; v++)
+    if (!known[v]) {
+      info.first_unsolved = v;
+      break;
+    }
+  info.first_blocked = m;
+  for (size_t j = 0; j < m; j++)
+    if (!is_step[j] && cnt_ab[j] + cnt_c[j] > 0) {
+      info.first_blocked = j;
+      break;
+    }
+  if (info.first_blocked < m) {
+    const size_t j = info.first_blocked;
+    uint32_t in_ab = ~0u;  // the unknown of a and b when there is one only
+    for (int w = 0; w < 2; w++)
+      for (uint32_t e = cs->h_row_ptr[w][j]; e < cs->h_row_ptr[w][j + 1]; e++)
+        if (cs->h_col[w][e] && !known[cs->h_col[w][e] - 1]) in_ab = cs->h_col[w][e] - 1;
+    uint32_t t = ~0u;
+    bool poly = false;
+    for (uint32_t e = cs->h_row_ptr[2][j]; e < cs->h_row_ptr[2][j + 1]; e++)
+      if (cs->h_col[2][e] && !known[cs->h_col[2][e] - 1]) {
+        t = cs->h_col[2][e] - 1;
+        if (!cs->h_pidx[2].empty() && cs->h_pidx[2][e] >= 0) poly = true;
+      }
+    if (cnt_c[j] == 1 && cnt_ab[j] == 1 && in_ab == t) info.blocked_reason = 5;
+    else if (cnt_ab[j] > 0) info.blocked_reason = 1;
+    else if (cnt_c[j] > 1) info.blocked_reason = 2;
+    else info.blocked_reason = poly ? 3 : 4;
+  }
+}
+
+// algorithmic bytes of the steps [s_lo, s_hi): the distinct wires read or written times S * 8, plus the CSR entries and the
+// schedule words touched; FP64 instructions per lane: a modular multiply-add per entry, the product and k^-1 per step
+static void launch_cost(const rs_ctx *ctx, const rs_r1cs_solve_plan *P, std::vector<uint32_t> &seen, uint32_t token, SolveLaunch &ln) {
+  const rs_r1cs *cs = P->cs;
+  double wires = 0, entries = 0;
+  for (size_t s = ln.s_lo; s < ln.s_hi; s++) {
+    const uint32_t j = P->rows[s];
+    if (seen[P->wires[s] + 1] != token) seen[P->wires[s] + 1] = token, wires++;
+    for (int w = 0; w < 3; w++)
+      for (uint32_t e = cs->h_row_ptr[w][j]; e < cs->h_row_ptr[w][j + 1]; e++) {
+        const uint32_t c = cs->h_col[w][e];
+        entries++;
+        if (c && seen[c] != token) seen[c] = token, wires++;
+      }
+  }
+  const double S = (double)ctx->ring_words(), steps = (double)(ln.s_hi - ln.s_lo);
+  ln.bytes = wires * S * 8 + entries * (4 + 8.0 * ctx->L) + steps * (8 + 6 * 4 + 8.0 * ctx->L);
+  ln.ops = 7.0 * (entries + 2 * steps) * S;
+}
+
+static void build_launches(const rs_ctx *ctx, rs_r1cs_solve_plan *P) {
+  const size_t n_levels = P->level_ptr.size() - 1, n_steps = P->rows.size();
+  const size_t chunks = (ctx->ring_words() / 2 + 255) / 256;
+  for (auto &l : P->launches) l.clear();
+  if (n_steps == 0 || chunks == 0) return;
+  for (size_t l = 0; l < n_levels; l++) P->launches[RS_SOLVE_LEVELS].push_back(SolveLaunch{0, P->level_ptr[l], P->level_ptr[l + 1], 0, 0});
+  P->launches[RS_SOLVE_WALK].push_back(SolveLaunch{1, 0, n_steps, 0, 0});
+  std::vector<SolveLaunch> &autol = P->launches[RS_SOLVE_AUTO];
+  for (size_t l = 0; l < n_levels; l++) {
+    const size_t lo = P->level_ptr[l], hi = P->level_ptr[l + 1];
+    if ((hi - lo) * chunks >= SOLVE_FILL_WORKGROUPS) autol.push_back(SolveLaunch{0, lo, hi, 0, 0});
+    else if (!autol.empty() && autol.back().kind == 1) autol.back().s_hi = hi;
+    else autol.push_back(SolveLaunch{1, lo, hi, 0, 0});
+  }
+  std::vector<uint32_t> seen(P->cs->n_vars + 1, 0);
+  uint32_t token = 0;
+  for (auto &list : P->launches)
+    for (SolveLaunch &ln : list) launch_cost(ctx, P, seen, ++token, ln);
+}
+
+template <class M>
+static void solve_run(rs_ctx *ctx, const rs_r1cs_solve_plan *P, uint64_t *d_asg, const std::vector<SolveLaunch> &launches, hipStream_t st) {
+  using T = typename ArithOf<M>::T;
+  const rs_r1cs *cs = P->cs;
+  SolveCsr<T> k;
+  for (int w = 0; w < 3; w++) {
+    k.rp[w] = cs->d_row_ptr[w];
+    k.col[w] = cs->d_col[w];
+    k.cf[w] = reinterpret_cast<const T *>(cs->d_coeff[w]);
+    k.nnz[w] = cs->nnz[w];
+    k.px[w] = cs->d_pidx[w];
+  }
+  k.ptab = reinterpret_cast<const T *>(cs->d_ptab);
+  const T *kinv = reinterpret_cast<const T *>(P->d_kinv);
+  const size_t n_steps = P->rows.size(), chunks = (ctx->ring_words() / 2 + 255) / 256;
+  for (const SolveLaunch &ln : launches) {
+    if (ln.kind == 0) {
+      size_t spw = SOLVE_STEPS_PER_WG;
+      while (spw > 1 && chunks * ((ln.s_hi - ln.s_lo + spw - 1) / spw) < 4096) spw >>= 1;
+      const size_t groups = (ln.s_hi - ln.s_lo + spw - 1) / spw;
+      RS_REQUIRE(chunks * groups < ((size_t)1 << 31), "level too wide for one launch of the solver");
+      ProfScope p(ctx, st, "solve_level", ln.bytes, ln.ops);
+      hipLaunchKernelGGL(solve_level_kernel<M>, dim3((unsigned)(chunks * groups)), dim3(256), 0, st, k, P->d_rows, P->d_wires, kinv, n_steps,
+                         ln.s_lo, ln.s_hi, d_asg, ctx->N, ctx->L, CtxArith<M>::qmod(ctx), (unsigned)groups, (unsigned)spw);
+    } else {
+      ProfScope p(ctx, st, "solve_walk", ln.bytes, ln.ops);
+      hipLaunchKernelGGL(solve_walk_kernel<M>, dim3((unsigned)chunks), dim3(256), 0, st, k, P->d_rows, P->d_wires, kinv, n_steps, ln.s_lo,
+                         ln.s_hi, d_asg, ctx->N, ctx->L, CtxArith<M>::qmod(ctx));
+    }
+    RS_HIP(hipGetLastError());
+  }
+}
+
+template <class M>
+static uint64_t konst_bits(uint64_t v, uint64_t p) {
+  const typename HostArith<M>::T c = HostArith<M>::konst(v, p);
+  uint64_t w;
+  static_assert(sizeof(c) == sizeof(w), "constants of both arithmetics travel as 64-bit words");
+  std::memcpy(&w, &c, sizeof(w));
+  return w;
+}
+
+}  // namespace rs
+
+using namespace rs;
+
+extern "C" {
+
+int rs_r1cs_solve_plan_create(rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *h_given, rs_r1cs_solve_plan **out, rs_r1cs_solve_info *h_info) {
+  RS_API_BEGIN_CTX(ctx)
+  RS_REQUIRE(cs && out && (h_given || cs->n_vars == 0), "null argument");
+  RS_REQUIRE(cs->L == ctx->L, "constraint system of another context");
+  struct Holder {  // frees a partly built plan when a check below throws
+    rs_r1cs_solve_plan *p;
+    ~Holder() { rs_r1cs_solve_plan_destroy(p); }
+  } holder{new rs_r1cs_solve_plan()};
+  rs_r1cs_solve_plan *P = holder.p;
+  P->ctx = ctx;
+  P->cs = cs;
+  std::vector<uint64_t> k;
+  build_schedule(ctx, cs, h_given, P, k);
+  // everything that indexes memory on the device, checked before any launch can use it
+  const size_t n = P->rows.size(), L = (size_t)ctx->L;
+  RS_REQUIRE(P->wires.size() == n && P->level_ptr.front() == 0 && P->level_ptr.back() == n, "inconsistent schedule");
+  for (size_t s = 0; s < n; s++) RS_REQUIRE(P->rows[s] < cs->m && P->wires[s] < cs->n_vars, "schedule index out of range");
+  for (size_t l = 0; l + 1 < P->level_ptr.size(); l++) RS_REQUIRE(P->level_ptr[l] < P->level_ptr[l + 1], "level pointers are not monotone");
+  if (n) {
+    std::vector<uint64_t> kinv(L * n);
+    for (size_t s = 0; s < n; s++)
+      for (size_t l = 0; l < L; l++) {
+        const uint64_t inv = host::invmod(k[s * L + l], ctx->q[l]);
+        kinv[l * n + s] = ctx->use_int ? konst_bits<ModI>(inv, ctx->q[l]) : konst_bits<Mod>(inv, ctx->q[l]);
+      }
+    RS_HIP(hipMalloc(&P->d_rows, sizeof(uint32_t) * n));
+    RS_HIP(hipMalloc(&P->d_wires, sizeof(uint32_t) * n));
+    RS_HIP(hipMalloc(&P->d_kinv, sizeof(uint64_t) * L * n));
+    RS_HIP(hipMemcpy(P->d_rows, P->rows.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    RS_HIP(hipMemcpy(P->d_wires, P->wires.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    RS_HIP(hipMemcpy(P->d_kinv, kinv.data(), sizeof(uint64_t) * L * n, hipMemcpyHostToDevice));
+  }
+  build_launches(ctx, P);
+  if (h_info) *h_info = P->info;
+  holder.p = nullptr;
+  *out = P;
+  RS_API_END
+}
+
+int rs_r1cs_solve_plan_steps(const rs_r1cs_solve_plan *plan, uint32_t *h_rows, uint32_t *h_wires, uint64_t *h_level_ptr) {
+  RS_API_BEGIN
+  RS_REQUIRE(plan, "null argument");
+  if (h_rows) std::copy(plan->rows.begin(), plan->rows.end(), h_rows);
+  if (h_wires) std::copy(plan->wires.begin(), plan->wires.end(), h_wires);
+  if (h_level_ptr) std::copy(plan->level_ptr.begin(), plan->level_ptr.end(), h_level_ptr);
+  RS_API_END
+}
+
+void rs_r1cs_solve_plan_destroy(rs_r1cs_solve_plan *plan) {
+  if (!plan) return;
+  if (plan->d_rows) (void)hipFree(plan->d_rows);
+  if (plan->d_wires) (void)hipFree(plan->d_wires);
+  if (plan->d_kinv) (void)hipFree(plan->d_kinv);
+  delete plan;
+}
+
+int rs_r1cs_solve(rs_ctx *ctx, const rs_r1cs_solve_plan *plan, uint64_t *d_assignment, int mode, rs_r1cs_solve_stats *h_stats,
+                  rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  RS_REQUIRE(plan && d_assignment, "null argument");
+  RS_REQUIRE(plan->ctx == ctx, "solve plan of another context");
+  RS_REQUIRE(mode == RS_SOLVE_AUTO || mode == RS_SOLVE_LEVELS || mode == RS_SOLVE_WALK, "unknown solve mode");
+  const std::vector<SolveLaunch> &launches = plan->launches[mode];
+  rs_r1cs_solve_stats stats{0, 0};
+  for (const SolveLaunch &ln : launches) (ln.kind == 0 ? stats.level_launches : stats.walk_launches)++;
+  if (!launches.empty()) {
+    std::unique_lock<std::mutex> lk(ctx->mu, std::defer_lock);
+    if (ctx->profiling) lk.lock();  // the record ProfScope appends to belongs to the holder of mu
+    RS_DISPATCH_ARITH(ctx, (solve_run<Mod>(ctx, plan, d_assignment, launches, S(stream))),
+                      (solve_run<ModI>(ctx, plan, d_assignment, launches, S(stream))));
+  }
+  if (h_stats) *h_stats = stats;
+  RS_API_END
+}
+
+}  // extern "C"

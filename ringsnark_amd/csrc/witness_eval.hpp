@@ -216,6 +216,59 @@ __device__ __forceinline__ void eval_row_pair(const uint32_t *__restrict__ row_p
   o1 = canon(a1, mod);
 }
 
+// eval_row_pair over the entries [e0, e1) of a row, WITHOUT the terms on column `skip` (the assignment solver,
+// r1cs_solve.hip: the row of c without its target; skip = ~0u keeps every term).  It loads the assignment rows of the terms it
+// keeps and no other -- the row of `skip` may hold anything -- through a pointer that is neither const nor restrict: the
+// caller may have stored to the rows it reads.  Same sums in the same order as eval_row_pair in its full mode.
+template <class M>
+__device__ __forceinline__ void eval_row_pair_skip(const uint32_t *__restrict__ col, const typename ArithOf<M>::T *__restrict__ coeff_limb,
+                                                   uint32_t e0, uint32_t e1, uint64_t *asg, size_t Si, size_t pair, uint32_t skip,
+                                                   const M mod, typename ArithOf<M>::T &o0, typename ArithOf<M>::T &o1,
+                                                   const int32_t *__restrict__ pidx, const typename ArithOf<M>::T *__restrict__ ptab) {
+  using T = typename ArithOf<M>::T;
+  T a0 = T(0), a1 = T(0);
+  int since = 0;
+  for (uint32_t e = e0; e < e1; e++) {
+    const uint32_t cv = col[e];
+    if (cv == skip) continue;
+    T cf0 = coeff_limb[e], cf1 = cf0;  // table constants
+    if (pidx) {
+      const int32_t pk = pidx[e];
+      if (pk >= 0) {
+        const T *pc = ptab + (size_t)pk * Si + 2 * pair;
+        cf0 = pc[0];
+        cf1 = pc[1];
+      }
+    }
+    if (cv == 0) {
+      a0 = addm(a0, konst_value(cf0, mod), mod);
+      a1 = addm(a1, konst_value(cf1, mod), mod);
+    } else {
+      const ulonglong2 v = reinterpret_cast<const ulonglong2 *>(asg + (size_t)(cv - 1) * Si)[pair];
+      a0 = addm(a0, mulmod(from_res<T>(v.x), cf0, mod), mod);
+      a1 = addm(a1, mulmod(from_res<T>(v.y), cf1, mod), mod);
+    }
+    if (++since == 4) {
+      since = 0;
+      a0 = reduce(a0, mod);
+      a1 = reduce(a1, mod);
+    }
+  }
+  o0 = canon(a0, mod);
+  o1 = canon(a1, mod);
+}
+
+// Workgroup `w` of `n` -> the position it takes in the (slot chunk, row group) order of the satisfaction check and the
+// assignment solver.  Blocks are dealt round-robin over the eight XCDs (b and b + 8 share one), so the blocks of one XCD get
+// a contiguous run of positions: one slot chunk, neighbouring row groups -- rows of real circuits share variables with their
+// neighbours, and the second reader of a wire then finds it in that XCD's L2 (measured on the check: 7 % on wide_r1cs at 2^13
+// constraints, nothing on the chain, whose rows share wires inside a group).  Bijective for every n (the plain
+// (w % 8) * ceil(n / 8) + w / 8 is not when n % 8 != 0).  Placement changes speed only.
+__device__ __forceinline__ unsigned xcd_position(unsigned w, unsigned n) {
+  const unsigned q = n >> 3, r = n & 7u, x = w & 7u;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (w >> 3);
+}
+
 // eval_row_pair for R rows (row0, row0 + step, ...) of one slot pair AT ONCE: the R chains of dependent loads advance together,
 // every load unconditional on a clamped index (loads under a lane predicate would be waited for inside their branch, one row
 // after the other), the terms a row does not have or does not want are dropped at the accumulation.  Same sums in the same

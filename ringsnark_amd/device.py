@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from .params import RingParams
-from .r1cs import R1CS, R1csCheck
+from .r1cs import R1CS, SOLVE_BLOCKED, R1csCheck, SolveInfo, given_mask
 
 
 def to_device(a: np.ndarray, device) -> torch.Tensor:
@@ -96,6 +96,39 @@ class DeviceR1CS:
         if getattr(self, "h", None) and self.dev.lib is not None:
             self.dev.lib.rs_r1cs_destroy(self.h)
             self.h = None
+
+
+SOLVE_MODES = {"auto": _lib.RS_SOLVE_AUTO, "levels": _lib.RS_SOLVE_LEVELS, "walk": _lib.RS_SOLVE_WALK}
+SolveStats = collections.namedtuple("SolveStats", "level_launches walk_launches")
+
+
+class SolvePlan:
+    """A solve plan on the device (rs_r1cs_solve_plan): the schedule that completes an assignment of `dcs` from the given
+    wires.  .info is a SolveInfo; close() (or garbage collection) frees it.  Keeps `dcs` alive: the plan reads its matrices."""
+
+    def __init__(self, dev, dcs, given):
+        self.dev, self.dcs = dev, dcs
+        mask = given_mask(dcs.cs, given)
+        h, info = C.c_void_p(), _lib.SolveInfo()
+        _lib.check(dev.lib.rs_r1cs_solve_plan_create(dev.h, dcs.h, mask.ctypes.data_as(_lib.u8p), C.byref(h), C.byref(info)))
+        self.h = h
+        self.info = SolveInfo(*[int(getattr(info, k)) for k, _ in _lib.SolveInfo._fields_])
+
+    def steps(self):
+        """([(constraint, variable)] in the order they run, level_ptr [n_levels + 1])"""
+        n = self.info.n_solved
+        rows, wires = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        lp = np.zeros(self.info.n_levels + 1, dtype=np.uint64)
+        _lib.check(self.dev.lib.rs_r1cs_solve_plan_steps(self.h, rows.ctypes.data_as(_lib.u32p), wires.ctypes.data_as(_lib.u32p),
+                                                         lp.ctypes.data_as(_lib.u64p)))
+        return [(int(r), int(w)) for r, w in zip(rows[:n], wires[:n])], [int(x) for x in lp]
+
+    def close(self):
+        if getattr(self, "h", None) and self.dev.lib is not None:
+            self.dev.lib.rs_r1cs_solve_plan_destroy(self.h)
+        self.h = None
+
+    __del__ = close
 
 
 IO_EVAL_TILE = 64  # rows per tile of rs_io_eval_at (csrc/verify.hip IO_TILE): its workspace is 2 * ceil(m / 64) ring elements
@@ -548,6 +581,26 @@ class Device:
                                           C.byref(rep), self.stream()))
         return R1csCheck(int(rep.n_violated), int(rep.first_row), int(rep.first_limb), int(rep.first_slot), int(rep.a), int(rep.b),
                          int(rep.c), flags)
+
+    def r1cs_solve_plan(self, dcs, given):
+        """The schedule that completes an assignment of `dcs` from the `given` wires (an iterable of 0-based variables or a
+        bool mask [n_vars]): rs_r1cs_solve_plan_create.  A plan with unsolved wires is still a plan; .info says what is
+        missing and why."""
+        return SolvePlan(self, dcs, given)
+
+    def r1cs_solve(self, plan, assignment, mode="auto", allow_partial=False):
+        """Fills the rows of the solved wires of `assignment` [n_vars][L][N] in place (rs_r1cs_solve) and returns
+        SolveStats(level_launches, walk_launches).  Rows that are neither given nor solved are never read and stay as they
+        are.  With unsolved wires it raises ValueError unless allow_partial."""
+        assert self._count(assignment, self.ring_words) == plan.dcs.n_vars, "the solver addresses every row of the assignment"
+        i = plan.info
+        if i.n_unsolved and not allow_partial:
+            raise ValueError("the given wires do not determine the assignment: %d of %d variables unsolved, first unsolved variable %d; "
+                             "first blocked constraint %d: %s" % (i.n_unsolved, plan.dcs.n_vars, i.first_unsolved, i.first_blocked,
+                                                                  SOLVE_BLOCKED[i.blocked_reason]))
+        stats = _lib.SolveStats()
+        _lib.check(self.lib.rs_r1cs_solve(self.h, plan.h, _ptr(assignment), SOLVE_MODES[mode], C.byref(stats), self.stream()))
+        return SolveStats(int(stats.level_launches), int(stats.walk_launches))
 
     def _require_satisfied(self, dcs, assignment):
         r = self.r1cs_check(dcs, assignment)

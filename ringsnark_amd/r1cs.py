@@ -111,6 +111,147 @@ def is_satisfied(cs: R1CS, assignment, q: List[int]) -> R1csCheck:
     return R1csCheck(n, row, limb, slot, int(ev[0, row, limb, slot]), int(ev[1, row, limb, slot]), int(ev[2, row, limb, slot]), flags)
 
 
+@dataclass
+class SolveInfo:
+    """What a solve plan reports (rs_r1cs_solve_info of ringsnark_amd/r1cs_solve.h, field for field)."""
+    n_given: int
+    n_solved: int
+    n_unsolved: int
+    first_unsolved: int  # lowest 0-based variable neither given nor solved; n_vars when there is none
+    n_levels: int
+    max_width: int
+    n_unused: int  # constraints that determine nothing (checks, or never ready)
+    first_blocked: int  # lowest constraint never ready that still holds an unknown wire; m when there is none
+    blocked_reason: int  # of first_blocked, a key of SOLVE_BLOCKED
+
+
+# csrc/r1cs_solve.hip: RS_SOLVE_AUTO gives a level to the level kernel when width * slot chunks (of 256 slot pairs) reaches this
+SOLVE_FILL_WORKGROUPS = 256
+SOLVE_BLOCKED = {0: "nothing is blocked", 1: "an unknown wire in a or b", 2: "several unknown wires in c",
+                 3: "a polynomial coefficient on the target", 4: "the target's coefficients sum to 0 modulo a ring prime",
+                 5: "the target also occurs in a or b"}
+
+
+def given_mask(cs: R1CS, given) -> np.ndarray:
+    """uint8 [n_vars] from a bool mask of that length or from an iterable of 0-based variables."""
+    g = np.asarray(list(given) if not isinstance(given, np.ndarray) else given)
+    if g.dtype == np.bool_:
+        assert g.shape == (cs.n_vars,), g.shape
+        return g.astype(np.uint8)
+    mask = np.zeros(cs.n_vars, dtype=np.uint8)
+    idx = g.astype(np.int64)
+    assert idx.size == 0 or (0 <= idx.min() and idx.max() < cs.n_vars), "given variable out of range"
+    mask[idx] = 1
+    return mask
+
+
+def solve_schedule(cs: R1CS, given, q: List[int]):
+    """The schedule of the assignment solver (ringsnark_amd/r1cs_solve.h), the host mirror of rs_r1cs_solve_plan_create.
+    Variables are 0-based (variable v is column v + 1; column 0 is the constant one).  Constraint j is ready when every wire
+    of a and b is known, c holds exactly one distinct unknown wire w, every c entry on w has a scalar coefficient and their
+    sum is non-zero modulo every q_l.  Given wires have level 0, a step's level is 1 + the highest level among the wires
+    its constraint reads, a wire is determined in the lowest level in which a constraint for it is ready and there by the
+    lowest such constraint; steps are ordered by (level, constraint).  Unknown-counters per constraint and a wire ->
+    constraint adjacency: O(nnz) apart from sorting each level.
+    Returns (steps [(constraint, variable)], level_ptr [n_levels + 1], SolveInfo)."""
+    m, nv = cs.m, cs.n_vars
+    known = given_mask(cs, given).astype(bool)
+    n_given = int(known.sum())
+    rp = {n: [int(x) for x in cs.mats[n][0]] for n in "abc"}
+    col = {n: [int(x) for x in cs.mats[n][1]] for n in "abc"}
+    unk_ab, unk_c = [set() for _ in range(m)], [set() for _ in range(m)]
+    adj = [[] for _ in range(nv)]  # wire -> (constraint, in c)
+    for j in range(m):
+        for n in "abc":
+            side = unk_c[j] if n == "c" else unk_ab[j]
+            for e in range(rp[n][j], rp[n][j + 1]):
+                v = col[n][e] - 1
+                if v >= 0 and not known[v] and v not in side:
+                    side.add(v)
+                    adj[v].append((j, n == "c"))
+    candidate = lambda j: not unk_ab[j] and len(unk_c[j]) == 1
+    pidx = None if cs.poly_idx is None else cs.poly_idx["c"]
+    coeff = cs.mats["c"][2]
+    steps, level_ptr, is_step, max_width = [], [0], [False] * m, 0
+    cand = [j for j in range(m) if candidate(j)]
+    while cand:
+        fresh = {}
+        for j in sorted(cand):
+            if not candidate(j):
+                continue
+            (t,) = unk_c[j]
+            if t in fresh:
+                continue  # a lower constraint of this level determines it
+            on_t = [e for e in range(rp["c"][j], rp["c"][j + 1]) if col["c"][e] == t + 1]
+            if pidx is not None and any(pidx[e] >= 0 for e in on_t):
+                continue
+            if any(sum(int(coeff[l, e]) for e in on_t) % int(q[l]) == 0 for l in range(len(q))):
+                continue
+            fresh[t] = j
+            is_step[j] = True
+            steps.append((j, t))
+        if not fresh:
+            break
+        level_ptr.append(len(steps))
+        max_width = max(max_width, len(fresh))
+        cand = []
+        for t in fresh:
+            known[t] = True
+        for t in fresh:
+            for j, in_c in adj[t]:
+                (unk_c if in_c else unk_ab)[j].discard(t)
+                if candidate(j):
+                    cand.append(j)
+    unsolved = [v for v in range(nv) if not known[v]]
+    blocked = [j for j in range(m) if not is_step[j] and (unk_ab[j] or unk_c[j])]
+    reason = 0
+    if blocked:
+        j = blocked[0]
+        if len(unk_c[j]) == 1 and unk_ab[j] == unk_c[j]:
+            reason = 5
+        elif unk_ab[j]:
+            reason = 1
+        elif len(unk_c[j]) > 1:
+            reason = 2
+        else:
+            (t,) = unk_c[j]
+            poly = pidx is not None and any(pidx[e] >= 0 for e in range(rp["c"][j], rp["c"][j + 1]) if col["c"][e] == t + 1)
+            reason = 3 if poly else 4
+    info = SolveInfo(n_given, len(steps), len(unsolved), unsolved[0] if unsolved else nv, len(level_ptr) - 1, max_width,
+                     m - len(steps), blocked[0] if blocked else m, reason)
+    return steps, level_ptr, info
+
+
+def solve(cs: R1CS, given, assignment, q: List[int]) -> np.ndarray:
+    """The assignment solver on the host in exact Python integers, the host mirror of rs_r1cs_solve: a copy of `assignment`
+    [n_vars][L][N] with the rows of the solved wires filled in,
+        w = (<a,(1,x)> * <b,(1,x)> - <c,(1,x)> without w) * k^-1   per limb and slot, canonical.
+    Reads given and already solved rows only; rows of unsolved wires are returned as they were."""
+    out = np.array(assignment, dtype=np.uint64)
+    L = len(q)
+    assert out.ndim == 3 and out.shape[0] == cs.n_vars and out.shape[1] == L, out.shape
+    steps, _, _ = solve_schedule(cs, given, q)
+
+    def row(name, j, l, skip):
+        rp, col, coeff = cs.mats[name]
+        pidx = None if cs.poly_idx is None else cs.poly_idx[name]
+        acc, k = np.zeros(out.shape[2], dtype=object), 0
+        for e in range(int(rp[j]), int(rp[j + 1])):
+            if int(col[e]) == skip:
+                k += int(coeff[l, e])
+                continue
+            cf = cs.poly_table[int(pidx[e]), l].astype(object) if pidx is not None and pidx[e] >= 0 else int(coeff[l, e])
+            acc = (acc + cf * (1 if col[e] == 0 else out[int(col[e]) - 1, l].astype(object))) % int(q[l])
+        return acc, k
+
+    for j, t in steps:
+        for l in range(L):
+            p = int(q[l])
+            (a, _), (b, _), (c, k) = row("a", j, l, -1), row("b", j, l, -1), row("c", j, l, t + 1)
+            out[t, l] = ((a * b - c) * pow(k % p, -1, p) % p).astype(np.uint64)
+    return out
+
+
 def chain_r1cs(m: int, q: List[int]) -> R1CS:
     """x_i * x_{i+1} = x_{i+2}, i < m; variables x_0..x_{m+1}; x_0, x_1 public (n_aux = m)."""
     rows = {"a": [[(i + 1, 1)] for i in range(m)], "b": [[(i + 2, 1)] for i in range(m)], "c": [[(i + 3, 1)] for i in range(m)]}
