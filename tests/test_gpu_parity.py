@@ -41,7 +41,7 @@ def test_ntt_matches_oracle(name):
     for modset, primes in ((_lib.RS_MOD_PLAIN, prm.q), (_lib.RS_MOD_COEFF, prm.Q)):
         for idx, p in enumerate(primes):
             t = O.NTT(logn, p)
-            batch = 3 if prm.N_enc < 16384 else 5  # the persistent wide kernels: more polynomials than one per workgroup slot is tested by the bandwidth runs
+            batch = 3 if prm.N_enc < 16384 else 5  # the persistent wide kernels: more polynomials than one per workgroup slot are in tests/test_launch_paths.py
             a = (rng.randint(0, 2**62, size=(batch, prm.N_enc), dtype=np.int64).astype(np.uint64)) % np.uint64(p)
             a[0, :4] = [0, 1, p - 1, p // 2]
             d = dev.put(a)
