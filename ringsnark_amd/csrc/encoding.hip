@@ -497,10 +497,17 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
     const int thr = enc_threads(ctx->logN_enc);
     set_max_dyn_lds((const void *)decrypt_dot_kernel_int, (int)lds);
     set_max_dyn_lds((const void *)crt_decode_kernel_int, (int)lds);
-    hipLaunchKernelGGL(decrypt_dot_kernel_int, dim3((unsigned)(count * L), K), dim3(thr), lds, st, d_enc, d_sk, V, K, ctx->logN_enc,
-                       ctx->d_coeff_tabs_i);
-    hipLaunchKernelGGL(crt_decode_kernel_int, dim3((unsigned)(count * L)), dim3(thr), lds, st, V, d_rings, ctx->N, L, ctx->logN_enc,
-                       cc, d_limbs, ctx->d_index_map, ctx->d_plain_tabs_i, (const uint64_t *)d_thr, tb, d_bits);
+    const double cts = (double)count * L, words = cts * K * n;  // ciphertexts; words of c0 (= of c1, = of V)
+    {
+      ProfScope p(ctx, st, "decrypt_dot_kernel_int", words * 8 * 3 + (double)K * n * 8, 0.0);
+      hipLaunchKernelGGL(decrypt_dot_kernel_int, dim3((unsigned)(count * L), K), dim3(thr), lds, st, d_enc, d_sk, V, K, ctx->logN_enc,
+                         ctx->d_coeff_tabs_i);
+    }
+    {
+      ProfScope p(ctx, st, "crt_decode_kernel_int", words * 8 + (d_rings ? cts * ctx->N * 8 : 0.0) + cts * 4, 0.0);
+      hipLaunchKernelGGL(crt_decode_kernel_int, dim3((unsigned)(count * L)), dim3(thr), lds, st, V, d_rings, ctx->N, L, ctx->logN_enc,
+                         cc, d_limbs, ctx->d_index_map, ctx->d_plain_tabs_i, (const uint64_t *)d_thr, tb, d_bits);
+    }
     RS_HIP(hipGetLastError());
     RS_HIP(hipStreamSynchronize(st));
     return noise_verdict(ctx, d_bits, count, tb, d_rings != nullptr, h_budget);
@@ -552,10 +559,18 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
   const int thr = enc_threads(ctx->logN_enc);
   set_max_dyn_lds((const void *)decrypt_dot_kernel, (int)lds);
   set_max_dyn_lds((const void *)crt_decode_kernel, (int)lds);
-  hipLaunchKernelGGL(decrypt_dot_kernel, dim3((unsigned)(count * L), K), dim3(thr), lds, st, d_enc, d_sk, V, K, ctx->logN_enc,
-                     ctx->d_coeff_tabs);
-  hipLaunchKernelGGL(crt_decode_kernel, dim3((unsigned)(count * L)), dim3(thr), lds, st, V, d_rings, ctx->N, L, ctx->logN_enc,
-                     cc, d_limbs, ctx->d_index_map, ctx->d_plain_tabs, (const double *)d_thr, tb, d_bits);
+  const double cts = (double)count * L, words = cts * K * n;  // ciphertexts; words of c0 (= of c1, = of V)
+  {
+    ProfScope p(ctx, st, "decrypt_dot_kernel", words * 8 * 3 + (double)K * n * 8, words * (7.0 + 7.0) + cts * K * ntt_fp64(n, ctx->logN_enc));
+    hipLaunchKernelGGL(decrypt_dot_kernel, dim3((unsigned)(count * L), K), dim3(thr), lds, st, d_enc, d_sk, V, K, ctx->logN_enc,
+                       ctx->d_coeff_tabs);
+  }
+  {
+    ProfScope p(ctx, st, "crt_decode_kernel", words * 8 + (d_rings ? cts * ctx->N * 8 : 0.0) + cts * 4,
+                cts * n * 7.0 * (K * (K - 1) / 2.0 + 2.0 * K) + (d_rings ? cts * ntt_fp64(n, ctx->logN_enc) : 0.0));
+    hipLaunchKernelGGL(crt_decode_kernel, dim3((unsigned)(count * L)), dim3(thr), lds, st, V, d_rings, ctx->N, L, ctx->logN_enc,
+                       cc, d_limbs, ctx->d_index_map, ctx->d_plain_tabs, (const double *)d_thr, tb, d_bits);
+  }
   RS_HIP(hipGetLastError());
   RS_HIP(hipStreamSynchronize(st));
   return noise_verdict(ctx, d_bits, count, tb, d_rings != nullptr, h_budget);

@@ -293,3 +293,148 @@ def extreme_case(name):
         _, encs, targets = aligned_terms(ctx, ALIGNED_D, 2000 + sorted(WORST_CASES).index(name), rings=[rings] * n_vecs)
         _ALIGNED[(name, "extreme")] = (ctx, rings, n_vecs, encs, targets, aligned_T(prm.Q))
     return _ALIGNED[(name, "extreme")]
+
+
+# ---- constructed noise polynomials for decode and the noise guard (tests/test_decode_boundaries.py) ---------------------
+# A ciphertext (c0, c1) of the encoding scheme decrypts to the polynomial v = c0 + c1 s mod Q (Q = prod Q_j), centred into
+# [-(Q - 1) / 2, (Q - 1) / 2]: its plaintext is v mod t, its noise budget max(0, bit_count(Q) - bit_count(max |v_x|) - 1).
+# Here v is CHOSEN, so both are known in Python integers, and it is put where the device's exact comparisons (the sign, by
+# the mixed-radix digits of floor(Q / 2); the bit length, by those of 2^b - 1) are ties or off a tie by one.
+def enc_modulus(Qs):
+    Q = 1
+    for p in Qs:
+        Q *= int(p)
+    return Q
+
+
+def noise_tb(Qs):
+    """bit_count(Q): the number of threshold rows 2^b - 1, b < tb, of the device's guard"""
+    return enc_modulus(Qs).bit_length()
+
+
+def mixed_radix(Qs, value):
+    """digits d_k of 0 <= value < Q with value = d_0 + Q_0 (d_1 + Q_1 (d_2 + ...))"""
+    assert 0 <= value < enc_modulus(Qs)
+    d = []
+    for p in Qs:
+        value, r = divmod(value, int(p))
+        d.append(r)
+    return d
+
+
+def centred(w, Q):
+    """the representative of w mod Q in [-(Q - 1) / 2, (Q - 1) / 2] (Q odd)"""
+    w %= Q
+    return w if w <= (Q - 1) // 2 else w - Q
+
+
+def boundary_values(Qs, reduced=False):
+    """[(kind, b, v)]: the centred integers v at which decoding and the guard decide by an exact comparison, no value twice.
+    kind "half": the residues (Q - 3) / 2 .. (Q + 3) / 2 around floor(Q / 2), where the sign changes; "tie": |v| = 2^b - 1, 2^b
+    or 2^b + 1, of either sign, around row b of the thresholds; "other": 0..3, -1, -2, and the residues 2^b + {-1, 0, 1} and
+    Q - 2^b + {1, 0, -1} whose centred magnitude is not of that form (b = tb - 1).  b: every row 0 <= b < tb; reduced (the
+    presets with many rows): the rows either side of the bit lengths of the partial products Q_0, Q_0 Q_1, .., where a
+    threshold gains a digit, and 1, 2, tb - 3, tb - 2, tb - 1."""
+    Q, tb = enc_modulus(Qs), noise_tb(Qs)
+    if reduced:
+        rows, part = {1, 2, tb - 3, tb - 2, tb - 1}, 1
+        for p in Qs[:-1]:
+            part *= int(p)
+            rows |= {part.bit_length() - 1, part.bit_length(), part.bit_length() + 1}
+        rows = sorted(rows)
+    else:
+        rows = range(tb)
+    out, seen = [], set()
+
+    def add(kind, b, w):
+        if 0 <= w < Q and centred(w, Q) not in seen:
+            seen.add(centred(w, Q))
+            out.append((kind, b, centred(w, Q)))
+
+    for w in ((Q - 3) // 2, (Q - 1) // 2, (Q + 1) // 2, (Q + 3) // 2):
+        add("half", None, w)
+    for b in rows:
+        for w in ((1 << b) - 1, 1 << b, (1 << b) + 1, Q - (1 << b) + 1, Q - (1 << b), Q - (1 << b) - 1):
+            add("tie" if 0 <= abs(centred(w, Q)) - ((1 << b) - 1) <= 2 and 0 <= w < Q else "other", b, w)
+    for w in (0, 1, 2, 3, Q - 1, Q - 2):
+        add("other", None, w)
+    return out
+
+
+def check_boundary_case(Qs, kind, b, v):
+    """That a value of boundary_values is the case its kind says, in Python's mixed-radix digits.
+    "tie": |v| >= 2^b is decided against the digits of 2^b - 1 -- by |v| > 2^b - 1 for v >= 0, by |v| - 1 >= 2^b - 1 for
+    v < 0 (whose magnitude Q - w is one more than the digit-wise complement of the residue w): the compared number has the
+    top K - 1 digits of 2^b - 1, and digit 0 alone holds the difference (-1, 0, 1 or 2).
+    "half": the residue has the digits of floor(Q / 2), or differs from them by its distance in digit 0 alone."""
+    Q = enc_modulus(Qs)
+    assert abs(v) <= (Q - 1) // 2, (kind, b, v)
+    if kind == "tie":
+        c, thr = (v if v >= 0 else -v - 1), (1 << b) - 1
+        assert -1 <= c - thr <= 2 and c >= 0, (b, v)
+        dc, dt = mixed_radix(Qs, c), mixed_radix(Qs, thr)
+        assert dc[1:] == dt[1:] and dc[0] - dt[0] == c - thr, (b, v, dc, dt)
+    elif kind == "half":
+        w, h = v % Q, (Q - 1) // 2
+        dw, dh = mixed_radix(Qs, w), mixed_radix(Qs, h)
+        assert abs(w - h) <= 2 and dw[1:] == dh[1:] and dw[0] - dh[0] == w - h, (v, dw, dh)
+    else:
+        assert kind == "other", kind
+
+
+def poly_residues(ctx, v):
+    """v mod Q_j of a polynomial of Python integers [N_enc]: uint64 [K][N_enc]"""
+    v = np.asarray(v, dtype=object)
+    assert v.shape == (ctx.N_enc,)
+    return np.stack([(v % Q).astype(np.uint64) for Q in ctx.Q])
+
+
+def noise_ciphertext(ctx, sk, v_per_limb, hidden, seed, plant=(), residues=None):
+    """One encoding element [L][2][K][N_enc] whose limb i decrypts to exactly the polynomial v_per_limb[i] -- a Python integer
+    (the constant polynomial) or N_enc of them -- with every |coefficient| <= (Q - 1) / 2:
+        c1_j = a_j,   c0_j = NTT_{Q_j}(v mod Q_j) - a_j s_j  (mod Q_j).
+    hidden False: a = 0 (the key plays no part); True: a uniform from `seed`, except at the positions `plant`, where a is
+    solved for so that the words the device multiplies and adds are at the top of their range: c1 s = Q_j - 1 at the
+    even-numbered ones, c0 = Q_j - 1 at the odd-numbered ones.  residues[i]: poly_residues of v_per_limb[i], if the
+    caller has them."""
+    n, Qfull = ctx.N_enc, enc_modulus(ctx.Q)
+    out = np.zeros(ctx.enc_shape(), dtype=np.uint64)
+    rng = np.random.RandomState(seed)
+    for i, v in enumerate(v_per_limb):
+        const = isinstance(v, int)
+        assert (abs(v) if const else max(abs(x) for x in v)) <= (Qfull - 1) // 2
+        res = None if const else (residues[i] if residues is not None else poly_residues(ctx, v))
+        for j, Q in enumerate(ctx.Q):
+            # the transform of a constant polynomial is that constant at every point
+            u = np.full(n, v % Q, dtype=np.uint64) if const else _ntt(n.bit_length() - 1, Q).fwd(res[j])
+            if not hidden:
+                out[i, 0, j] = u
+                continue
+            a = rng.randint(0, Q, size=n, dtype=np.int64).astype(object)
+            s = sk[j].astype(object)
+            for k, x in enumerate(plant):
+                assert s[x] != 0
+                a[x] = ((Q - 1) if k % 2 == 0 else (int(u[x]) + 1)) * pow(int(s[x]), -1, Q) % Q
+            out[i, 1, j] = a.astype(np.uint64)
+            out[i, 0, j] = ((u.astype(object) - a * s) % Q).astype(np.uint64)
+            for k, x in enumerate(plant):
+                assert int(a[x]) * int(s[x]) % Q == Q - 1 if k % 2 == 0 else int(out[i, 0, j, x]) == Q - 1
+    return out
+
+
+def expected_budget(ctx, v_per_limb):
+    """max(0, bit_count(Q) - bit_count(max_x |v_x|) - 1) per limb, in Python integers"""
+    tb = noise_tb(ctx.Q)
+    return [max(0, tb - (abs(v) if isinstance(v, int) else max(abs(x) for x in v)).bit_length() - 1) for v in v_per_limb]
+
+
+def expected_decode(ctx, v_per_limb):
+    """the ring element [L][N] an element of noise_ciphertext decodes to: limb i is the batch decoding of v mod q_i -- for a
+    constant polynomial that constant in every slot, no oracle involved"""
+    out = np.empty(ctx.ring_shape(), dtype=np.uint64)
+    for i, v in enumerate(v_per_limb):
+        if isinstance(v, int):
+            out[i] = v % ctx.q[i]
+        else:
+            out[i] = ctx.batch_decode(i, (np.asarray(v, dtype=object) % ctx.q[i]).astype(np.uint64))
+    return out
