@@ -222,6 +222,17 @@ BATCH_SIGNATURES = {  # every function of include/ringsnark_amd/batch.h
     "rs_prove_batch_bytes": (C.c_int, [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
 }
 
+MODSWITCH_SIGNATURES = {  # every function of include/ringsnark_amd/modswitch.h
+    "rs_enc_mod_switch": (C.c_int, [vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp]),
+    "rs_enc_decode_level": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, vp, vp]),
+    "rs_enc_noise_budget_level": (C.c_int, [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(C.c_int), vp]),
+    "rs_enc_wire_size_level": (C.c_size_t, [vp, C.c_int, C.c_size_t]),
+    "rs_enc_serialize_level": (C.c_int, [vp, C.c_int, vp, u8p, C.c_size_t, vp, C.c_size_t, vp]),
+    "rs_enc_deserialize_level": (C.c_int, [vp, vp, C.c_size_t, vp, u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int), vp]),
+    "rs_groth16_verify_level": (C.c_int, [vp, vp, C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(VerifyReport), vp]),
+    "rs_rinocchio_verify_level": (C.c_int, [vp, vp, C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(VerifyReport), vp]),
+}
+
 _lib = None
 
 
@@ -236,7 +247,7 @@ def load():
             "the HIP library is the only implementation, there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **SOLVE_SIGNATURES, **VERIFY_SIGNATURES,
-                              **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES}.items():
+                              **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES, **MODSWITCH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

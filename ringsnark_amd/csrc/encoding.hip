@@ -54,6 +54,8 @@ struct CrtLimb {
   Mod tmod;
   double Qk_mod_t[RS_MAX_K];
   double Q_mod_t;
+  double F;   // level factor prod_{j >= K} Q_j mod t of a decode below the context's level (modswitch.h)
+  int scale;  // 0: the context's own level, F = 1 and no product is made
 };
 
 // ---- the noise guard of EncodingElem::decode (seal_ring.tcc:443-454) ----------------------------------------------
@@ -121,7 +123,9 @@ crt_decode_kernel(const double *__restrict__ V, uint64_t *__restrict__ rings, in
     double r = 0.0;
     for (int k = K - 1; k >= 0; k--) r = reduce(mulmod(r, cl.Qk_mod_t[k], tmod) + reduce(d[k], tmod), tmod);
     if (upper) r -= cl.Q_mod_t;
-    s[pidx(x)] = reduce(r, tmod);
+    r = reduce(r, tmod);
+    if (cl.scale) r = reduce(mulmod(r, cl.F, tmod), tmod);  // SEAL's correction_factor of a switched ciphertext
+    s[pidx(x)] = r;
   }
   atomicMax(&s_bits, my_bits);
   __syncthreads();
@@ -223,6 +227,8 @@ struct CrtLimbI {
   ModI tmod;
   uint64_t Qk_mod_t[RS_MAX_K];  // Montgomery form
   uint64_t Q_mod_t;             // value
+  uint64_t F;                   // level factor, Montgomery form (CrtLimb)
+  int scale;
 };
 
 __global__ void __launch_bounds__(1024)
@@ -263,6 +269,7 @@ crt_decode_kernel_int(const uint64_t *__restrict__ V, uint64_t *__restrict__ rin
     uint64_t r = 0;
     for (int k = K - 1; k >= 0; k--) r = addm(mulmod(r, cl.Qk_mod_t[k], tmod), d[k] % tmod.p, tmod);
     if (upper) r = subm(r, cl.Q_mod_t, tmod);
+    if (cl.scale) r = mulmod(r, cl.F, tmod);
     s[pidx(x)] = r;
   }
   atomicMax(&s_bits, my_bits);
@@ -358,18 +365,18 @@ struct BigU {
   }
 };
 
-// thr[b * RS_MAX_K + k] = digit k of 2^b - 1; returns bit_count(Q)
-static int noise_thresholds(const rs_ctx *ctx, std::vector<uint64_t> &thr) {
+// thr[b * RS_MAX_K + k] = digit k of 2^b - 1; returns bit_count(Q), Q the product of the first K primes
+static int noise_thresholds(const rs_ctx *ctx, int K, std::vector<uint64_t> &thr) {
   BigU Q;
   Q.w[0] = 1;
-  for (int k = 0; k < ctx->K; k++) Q.mul_add(ctx->Q[k], 0);
+  for (int k = 0; k < K; k++) Q.mul_add(ctx->Q[k], 0);
   const int tb = Q.bits();
   thr.assign((size_t)tb * RS_MAX_K, 0);
   for (int b = 0; b < tb; b++) {
     BigU v;  // 2^b - 1
     for (int i = 0; i < b / 64; i++) v.w[i] = ~0ull;
     if (b % 64) v.w[b / 64] = (1ull << (b % 64)) - 1;
-    for (int k = 0; k < ctx->K; k++) thr[(size_t)b * RS_MAX_K + k] = v.divmod(ctx->Q[k]);
+    for (int k = 0; k < K; k++) thr[(size_t)b * RS_MAX_K + k] = v.divmod(ctx->Q[k]);
   }
   return tb;
 }
@@ -378,25 +385,25 @@ static int noise_thresholds(const rs_ctx *ctx, std::vector<uint64_t> &thr) {
 
 using namespace rs;
 
+// rs::decode_impl (declared in rs_internal.hpp, defined below; modswitch.hip and verify.hip call it too):
 // EncodingElem::decode and Decryptor::invariant_noise_budget share everything up to the centred composition.
-// d_rings == nullptr: budgets only.  h_budget [count * L] (may be null).  Returns RS_ERR_NOISE -- after writing every
+// d_rings == nullptr: budgets only.  h_budget [count * L] (may be null).  Throws RS_ERR_NOISE -- after writing every
 // decoding -- when d_rings is given and a ciphertext has no budget left (seal_ring.tcc:446-454).
-static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
-                       rs_stream stream);
-
+// K: the level -- the first K primes of the context, d_enc [count][L][2][K][N_enc]; below ctx->K the decoding is
+// multiplied by the level factor (modswitch.h).
 extern "C" {
 
 int rs_enc_decode(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
   RS_REQUIRE(ctx && d_sk && d_enc && d_rings, "null argument");
-  return decode_impl(ctx, d_sk, d_enc, count, d_rings, nullptr, stream);
+  return decode_impl(ctx, ctx->K, d_sk, d_enc, count, d_rings, nullptr, stream);
   RS_API_END
 }
 
 int rs_enc_noise_budget(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, int *h_budget, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
   RS_REQUIRE(ctx && d_sk && d_enc && h_budget, "null argument");
-  return decode_impl(ctx, d_sk, d_enc, count, nullptr, h_budget, stream);
+  return decode_impl(ctx, ctx->K, d_sk, d_enc, count, nullptr, h_budget, stream);
   RS_API_END
 }
 
@@ -421,16 +428,16 @@ static int noise_verdict(rs_ctx *ctx, const int *d_bits, size_t count, int tb, b
   return RS_OK;
 }
 
-static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
-                       rs_stream stream) {
+int rs::decode_impl(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
+                    rs_stream stream) {
   if (count == 0) return RS_OK;
   WsScope ws_scope(ctx, S(stream));  // holds ctx->mu: the lazily built constants below are built once
-  // Constants of the context that only decoding reads are built at the first call and kept on the device: the digits of
+  // Constants of the (context, level) that only decoding reads are built at the first call and kept on the device: the digits of
   // 2^b - 1 here, the per-limb CRT constants below.  With the table arrays of the context itself, a warm decode makes no
   // hipMalloc / hipFree and no pageable upload (each an implicit device-wide synchronisation; round-5 advice).
-  if (!ctx->d_noise_thr) {
+  if (!ctx->d_noise_thr[K]) {
     std::vector<uint64_t> thr_h;
-    ctx->noise_tb = noise_thresholds(ctx, thr_h);
+    ctx->noise_tb[K] = noise_thresholds(ctx, K, thr_h);
     if (!ctx->use_int)
       for (auto &x : thr_h) {  // digits < Q_k < 2^50: exact doubles
         const double d = (double)x;
@@ -442,12 +449,12 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
       (void)hipFree(p);
       throw rs::Error(RS_ERR_HIP, "upload of the noise-threshold table failed");
     }
-    ctx->d_noise_thr = p;
+    ctx->d_noise_thr[K] = p;
   }
-  const int tb = ctx->noise_tb;
-  void *d_thr = ctx->d_noise_thr;
+  const int tb = ctx->noise_tb[K];
+  void *d_thr = ctx->d_noise_thr[K];
   int *d_bits = (int *)ws_get(ctx, WS_NOISE_BITS, sizeof(int) * count * (size_t)ctx->L);
-  const int L = ctx->L, K = ctx->K, n = ctx->N_enc;
+  const int L = ctx->L, n = ctx->N_enc;
   hipStream_t st = S(stream);
   if (ctx->use_int) {  // the same composition on the integer arithmetic
     using namespace host;
@@ -466,7 +473,7 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
       const uint64_t Qk = ctx->Q[k];
       cc.Qmod[k] = HostArith<ModI>::make(Qk);
       uint64_t prod = 1 % Qk;
-      for (int i = 0; i < k; i++) prod = mulmod(prod, ctx->Q[i] % Qk, Qk);
+      for (int i = 0; i < k; i++) prod = host::mulmod(prod, ctx->Q[i] % Qk, Qk);
       cc.prod_inv[k] = HostArith<ModI>::konst(k ? invmod(prod, Qk) : 1, Qk);
       for (int i = 0; i < K; i++) cc.Qi_mod_Qk[i][k] = HostArith<ModI>::konst(ctx->Q[i] % Qk, Qk);
     }
@@ -478,20 +485,24 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
       uint64_t Qm = 1 % t;
       for (int k = 0; k < K; k++) {
         hl[i].Qk_mod_t[k] = HostArith<ModI>::konst(ctx->Q[k] % t, t);
-        Qm = mulmod(Qm, ctx->Q[k] % t, t);
+        Qm = host::mulmod(Qm, ctx->Q[k] % t, t);
       }
       hl[i].Q_mod_t = Qm;
+      uint64_t F = 1 % t;
+      for (int k = K; k < ctx->K; k++) F = host::mulmod(F, ctx->Q[k] % t, t);
+      hl[i].F = HostArith<ModI>::konst(F, t);
+      hl[i].scale = K < ctx->K;
     }
-    if (!ctx->d_crt_limbs) {
+    if (!ctx->d_crt_limbs[K]) {
       void *p = nullptr;
       RS_HIP(hipMalloc(&p, sizeof(CrtLimbI) * L));
       if (hipMemcpy(p, hl.data(), sizeof(CrtLimbI) * L, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(p);
         throw rs::Error(RS_ERR_HIP, "upload of the CRT constants failed");
       }
-      ctx->d_crt_limbs = p;
+      ctx->d_crt_limbs[K] = p;
     }
-    const CrtLimbI *d_limbs = static_cast<const CrtLimbI *>(ctx->d_crt_limbs);
+    const CrtLimbI *d_limbs = static_cast<const CrtLimbI *>(ctx->d_crt_limbs[K]);
     uint64_t *V = (uint64_t *)ws_get(ctx, WS_STAGE_ROWS, count * (size_t)L * K * n * sizeof(uint64_t));
     const size_t lds = padded_len((size_t)n) * sizeof(uint64_t);
     const int thr = enc_threads(ctx->logN_enc);
@@ -529,7 +540,7 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
     const uint64_t Qk = ctx->Q[k];
     cc.Qmod[k] = Mod{(double)Qk, 1.0 / (double)Qk};
     uint64_t prod = 1 % Qk;
-    for (int i = 0; i < k; i++) prod = mulmod(prod, ctx->Q[i] % Qk, Qk);
+    for (int i = 0; i < k; i++) prod = host::mulmod(prod, ctx->Q[i] % Qk, Qk);
     cc.prod_inv[k] = k ? balanced(invmod(prod, Qk), Qk) : 1.0;
     for (int i = 0; i < K; i++) cc.Qi_mod_Qk[i][k] = balanced(ctx->Q[i] % Qk, Qk);
   }
@@ -540,20 +551,24 @@ static int decode_impl(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc,
     uint64_t Qm = 1 % t;
     for (int k = 0; k < K; k++) {
       hl[i].Qk_mod_t[k] = balanced(ctx->Q[k] % t, t);
-      Qm = mulmod(Qm, ctx->Q[k] % t, t);
+      Qm = host::mulmod(Qm, ctx->Q[k] % t, t);
     }
     hl[i].Q_mod_t = balanced(Qm, t);
+    uint64_t F = 1 % t;
+    for (int k = K; k < ctx->K; k++) F = host::mulmod(F, ctx->Q[k] % t, t);
+    hl[i].F = balanced(F, t);
+    hl[i].scale = K < ctx->K;
   }
-  if (!ctx->d_crt_limbs) {
+  if (!ctx->d_crt_limbs[K]) {
     void *p = nullptr;
     RS_HIP(hipMalloc(&p, sizeof(CrtLimb) * L));
     if (hipMemcpy(p, hl.data(), sizeof(CrtLimb) * L, hipMemcpyHostToDevice) != hipSuccess) {
       (void)hipFree(p);
       throw rs::Error(RS_ERR_HIP, "upload of the CRT constants failed");
     }
-    ctx->d_crt_limbs = p;
+    ctx->d_crt_limbs[K] = p;
   }
-  const CrtLimb *d_limbs = static_cast<const CrtLimb *>(ctx->d_crt_limbs);
+  const CrtLimb *d_limbs = static_cast<const CrtLimb *>(ctx->d_crt_limbs[K]);
   double *V = (double *)ws_get(ctx, WS_STAGE_ROWS, count * (size_t)L * K * n * sizeof(double));
   const size_t lds = padded_len((size_t)n) * sizeof(double);
   const int thr = enc_threads(ctx->logN_enc);
@@ -618,87 +633,89 @@ int rs_enc_encode(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_rings, si
 //   u8     empty[count]                1 = EMPTY element (seal_ring.tcc:412,432), payload all zero
 //   pad to a multiple of 8 bytes
 //   u64    payload[count][L][2][K][N_enc]   canonical residues, the layout of the ABI
+// A stream of level K (modswitch.h) has K and Q[:K] in its header and K rows per component: exactly what a context
+// created on the truncated prime list writes.  The functions below take the level; the context's own is ctx->K.
 namespace rs {
 static const char kMagic[8] = {'R', 'S', 'N', 'K', 'E', 'N', 'C', '1'};
-static size_t wire_header_bytes(const rs_ctx *ctx, size_t count) {
-  const size_t raw = 8 + 16 + 8 * (size_t)(ctx->L + ctx->K) + 8 + count;
+static size_t wire_fixed_bytes(const rs_ctx *ctx, int K) { return 24 + 8 * (size_t)(ctx->L + K) + 8; }
+static size_t wire_header_bytes(const rs_ctx *ctx, int K, size_t count) {
+  const size_t raw = wire_fixed_bytes(ctx, K) + count;
   return (raw + 7) & ~(size_t)7;
 }
-}  // namespace rs
+static size_t level_enc_words(const rs_ctx *ctx, int K) { return (size_t)ctx->L * 2 * K * ctx->N_enc; }
 
-extern "C" {
-
-size_t rs_enc_wire_size(const rs_ctx *ctx, size_t count) {
-  if (!ctx) return 0;
-  return wire_header_bytes(ctx, count) + count * ctx->enc_words() * sizeof(uint64_t);
+size_t wire_size(const rs_ctx *ctx, int K, size_t count) {
+  return wire_header_bytes(ctx, K, count) + count * level_enc_words(ctx, K) * sizeof(uint64_t);
 }
 
-int rs_enc_serialize(rs_ctx *ctx, const uint64_t *d_enc, const uint8_t *h_empty, size_t count, void *h_buf, size_t buf_bytes,
-                     rs_stream stream) {
-  RS_API_BEGIN_CTX(ctx)
+void serialize_run(rs_ctx *ctx, int K, const uint64_t *d_enc, const uint8_t *h_empty, size_t count, void *h_buf, size_t buf_bytes,
+                   hipStream_t st) {
   RS_REQUIRE(ctx && h_buf && (d_enc || count == 0), "null argument");
-  RS_REQUIRE(buf_bytes >= rs_enc_wire_size(ctx, count), "buffer too small (rs_enc_wire_size)");
+  RS_REQUIRE(buf_bytes >= wire_size(ctx, K, count), "buffer too small (rs_enc_wire_size)");
   uint8_t *p = (uint8_t *)h_buf;
-  const size_t hb = wire_header_bytes(ctx, count);
+  const size_t hb = wire_header_bytes(ctx, K, count), enc_bytes = level_enc_words(ctx, K) * sizeof(uint64_t);
   memset(p, 0, hb);
   memcpy(p, kMagic, 8);
-  const uint32_t dims[4] = {(uint32_t)ctx->N, (uint32_t)ctx->L, (uint32_t)ctx->N_enc, (uint32_t)ctx->K};
+  const uint32_t dims[4] = {(uint32_t)ctx->N, (uint32_t)ctx->L, (uint32_t)ctx->N_enc, (uint32_t)K};
   memcpy(p + 8, dims, 16);
   memcpy(p + 24, ctx->q, 8 * (size_t)ctx->L);
-  memcpy(p + 24 + 8 * (size_t)ctx->L, ctx->Q, 8 * (size_t)ctx->K);
+  memcpy(p + 24 + 8 * (size_t)ctx->L, ctx->Q, 8 * (size_t)K);
   const uint64_t c64 = count;
-  uint8_t *q = p + 24 + 8 * (size_t)(ctx->L + ctx->K);
+  uint8_t *q = p + 24 + 8 * (size_t)(ctx->L + K);
   memcpy(q, &c64, 8);
   for (size_t i = 0; i < count; i++) q[8 + i] = h_empty ? (h_empty[i] ? 1 : 0) : 0;
   if (count) {
-    RS_HIP(hipMemcpyAsync(p + hb, d_enc, count * ctx->enc_words() * sizeof(uint64_t), hipMemcpyDeviceToHost, S(stream)));
-    RS_HIP(hipStreamSynchronize(S(stream)));
+    RS_HIP(hipMemcpyAsync(p + hb, d_enc, count * enc_bytes, hipMemcpyDeviceToHost, st));
+    RS_HIP(hipStreamSynchronize(st));
     if (h_empty)
       for (size_t i = 0; i < count; i++)
-        if (h_empty[i]) memset(p + hb + i * ctx->enc_words() * sizeof(uint64_t), 0, ctx->enc_words() * sizeof(uint64_t));
+        if (h_empty[i]) memset(p + hb + i * enc_bytes, 0, enc_bytes);
   }
-  RS_API_END
 }
 
-int rs_enc_deserialize(rs_ctx *ctx, const void *h_buf, size_t buf_bytes, uint64_t *d_enc, uint8_t *h_empty, size_t capacity,
-                       size_t *h_count, rs_stream stream) {
-  RS_API_BEGIN_CTX(ctx)
+// K_want: the level the stream must have, or 0: any 1 <= K <= ctx->K, reported in *K_found
+void deserialize_run(rs_ctx *ctx, int K_want, const void *h_buf, size_t buf_bytes, uint64_t *d_enc, uint8_t *h_empty, size_t capacity,
+                     size_t *h_count, int *K_found, hipStream_t st) {
   RS_REQUIRE(ctx && h_buf && h_count, "null argument");
   const uint8_t *p = (const uint8_t *)h_buf;
-  const size_t fixed = 24 + 8 * (size_t)(ctx->L + ctx->K) + 8;
-  RS_REQUIRE(buf_bytes >= fixed, "truncated header");
+  RS_REQUIRE(buf_bytes >= (K_want ? wire_fixed_bytes(ctx, K_want) : 24), "truncated header");
   RS_REQUIRE(memcmp(p, kMagic, 8) == 0, "bad magic: not a ringsnark_amd encoding stream");
   uint32_t dims[4];
   memcpy(dims, p + 8, 16);
-  RS_REQUIRE((int)dims[0] == ctx->N && (int)dims[1] == ctx->L && (int)dims[2] == ctx->N_enc && (int)dims[3] == ctx->K,
+  RS_REQUIRE((int)dims[0] == ctx->N && (int)dims[1] == ctx->L && (int)dims[2] == ctx->N_enc &&
+                 (K_want ? dims[3] == (uint32_t)K_want : dims[3] >= 1 && dims[3] <= (uint32_t)ctx->K),
              "stream was written for different ring / encoding dimensions");
-  RS_REQUIRE(memcmp(p + 24, ctx->q, 8 * (size_t)ctx->L) == 0 && memcmp(p + 24 + 8 * (size_t)ctx->L, ctx->Q, 8 * (size_t)ctx->K) == 0,
+  const int K = (int)dims[3];
+  const size_t fixed = wire_fixed_bytes(ctx, K);
+  RS_REQUIRE(buf_bytes >= fixed, "truncated header");
+  RS_REQUIRE(memcmp(p + 24, ctx->q, 8 * (size_t)ctx->L) == 0 && memcmp(p + 24 + 8 * (size_t)ctx->L, ctx->Q, 8 * (size_t)K) == 0,
              "stream was written for different moduli");
   uint64_t c64;
-  memcpy(&c64, p + 24 + 8 * (size_t)(ctx->L + ctx->K), 8);
+  memcpy(&c64, p + 24 + 8 * (size_t)(ctx->L + K), 8);
   // The count is untrusted: bound it by what the buffer can hold BEFORE any size arithmetic (every
   // element costs one flag byte + enc_bytes of payload), so that nothing below can wrap.
-  const size_t enc_bytes = ctx->enc_words() * sizeof(uint64_t);
+  const size_t per = level_enc_words(ctx, K), enc_bytes = per * sizeof(uint64_t);
   RS_REQUIRE(c64 <= (uint64_t)((buf_bytes - fixed) / (1 + enc_bytes)), "truncated payload");
   const size_t count = (size_t)c64;
-  RS_REQUIRE(buf_bytes >= rs_enc_wire_size(ctx, count), "truncated payload");
+  RS_REQUIRE(buf_bytes >= wire_size(ctx, K, count), "truncated payload");
   const uint8_t *em = p + fixed;
-  const size_t hb = wire_header_bytes(ctx, count);
+  const size_t hb = wire_header_bytes(ctx, K, count);
   for (size_t i = 0; i < count; i++) RS_REQUIRE(em[i] <= 1, "corrupt empty flag");
   for (size_t i = fixed + count; i < hb; i++) RS_REQUIRE(p[i] == 0, "non-zero header padding");
   if (!d_enc) {  // size query (header validated)
     *h_count = count;
-    return RS_OK;
+    if (K_found) *K_found = K;
+    return;
   }
   RS_REQUIRE(capacity >= count, "destination holds fewer elements than the stream");
   const uint64_t *payload = (const uint64_t *)(p + hb);
   // canonical-residue check on the host: a proof from the wire is untrusted input
-  const size_t n = (size_t)ctx->N_enc, per = ctx->enc_words();
+  const size_t n = (size_t)ctx->N_enc;
   for (size_t i = 0; i < count; i++)
     for (int l = 0; l < ctx->L; l++)
       for (int c = 0; c < 2; c++)
-        for (int j = 0; j < ctx->K; j++) {
-          const uint64_t *row = payload + i * per + (((size_t)l * 2 + c) * ctx->K + j) * n;
+        for (int j = 0; j < K; j++) {
+          const uint64_t *row = payload + i * per + (((size_t)l * 2 + c) * K + j) * n;
           const uint64_t Qj = ctx->Q[j];
           if (em[i]) {  // EMPTY element (seal_ring.tcc:412,432): the payload must be all zero
             for (size_t x = 0; x < n; x++) RS_REQUIRE(row[x] == 0, "non-zero payload of an EMPTY element");
@@ -707,12 +724,34 @@ int rs_enc_deserialize(rs_ctx *ctx, const void *h_buf, size_t buf_bytes, uint64_
           }
         }
   if (count) {
-    RS_HIP(hipMemcpyAsync(d_enc, payload, count * per * sizeof(uint64_t), hipMemcpyHostToDevice, S(stream)));
-    RS_HIP(hipStreamSynchronize(S(stream)));
+    RS_HIP(hipMemcpyAsync(d_enc, payload, count * per * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    RS_HIP(hipStreamSynchronize(st));
   }
   // outputs are written only after every check has passed
   if (h_empty) memcpy(h_empty, em, count);
   *h_count = count;
+  if (K_found) *K_found = K;
+}
+}  // namespace rs
+
+extern "C" {
+
+size_t rs_enc_wire_size(const rs_ctx *ctx, size_t count) {
+  if (!ctx) return 0;
+  return wire_size(ctx, ctx->K, count);
+}
+
+int rs_enc_serialize(rs_ctx *ctx, const uint64_t *d_enc, const uint8_t *h_empty, size_t count, void *h_buf, size_t buf_bytes,
+                     rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  serialize_run(ctx, ctx->K, d_enc, h_empty, count, h_buf, buf_bytes, S(stream));
+  RS_API_END
+}
+
+int rs_enc_deserialize(rs_ctx *ctx, const void *h_buf, size_t buf_bytes, uint64_t *d_enc, uint8_t *h_empty, size_t capacity,
+                       size_t *h_count, rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  deserialize_run(ctx, ctx->K, h_buf, buf_bytes, d_enc, h_empty, capacity, h_count, nullptr, S(stream));
   RS_API_END
 }
 

@@ -160,6 +160,8 @@ enum WsSlot {
                      // The verifiers call rs_enc_decode in a scope of its own, the provers never decode.
   WS_BC_PRODUCTS,    // bc_h, bc2_h: the block products before the H patch, [columns][2M].  A plan is either bc or bc2.
   WS_KEYGEN_STAGE,   // keygen_run (keygen.hip) with a host-resident key: the two staging buffers of encoded tiles, [2][tile] encoding elements (ciphertexts only, nothing secret)
+  WS_MODSWITCH_LEVELS,  // mod_switch_run (modswitch.hip): the intermediate levels of a switch of more than one step, two buffers used in turn,
+                     // [count][L][2][K_in - 1][N_enc] and [count][L][2][K_in - 2][N_enc]
   WS_COUNT
 };
 
@@ -233,11 +235,12 @@ struct rs_ctx {
   rs::Mod *d_qmod = nullptr;  // [L]
   rs::Mod *d_Qmod = nullptr;  // [K]
   uint64_t *d_qint = nullptr, *d_Qint = nullptr;  // q[L], Q[K] as plain integers
-  // decode / noise guard (encoding.hip): constants of the (context) built at the first rs_enc_decode / rs_enc_noise_budget and
-  // kept -- the digit table of 2^b - 1 for every b < bit_count(Q) in the context's arithmetic, the per-limb CRT constants
-  void *d_noise_thr = nullptr;
-  int noise_tb = 0;
-  void *d_crt_limbs = nullptr;
+  // decode / noise guard (encoding.hip): constants of the (context, level) built at the first decode / noise budget of that
+  // level and kept -- the digit table of 2^b - 1 for every b < bit_count(Q) in the context's arithmetic, the per-limb CRT
+  // constants.  Index: the level, i.e. the number of leading primes (modswitch.h); [K] is the context's own.
+  void *d_noise_thr[RS_MAX_K + 1] = {nullptr};
+  int noise_tb[RS_MAX_K + 1] = {0};
+  void *d_crt_limbs[RS_MAX_K + 1] = {nullptr};
   std::mutex mu;
   std::map<std::pair<size_t, uint64_t>, rs::WitnessPlan *> plans;  // keyed by (m, plan_knob_sig()), witness_plan.hip get_plan
   // workspace cache (grown on demand, per context; calls that need workspace serialise on mu)
@@ -384,7 +387,18 @@ void r1cs_evaluate_run(rs_ctx *ctx, const rs_r1cs *cs, int which, int mode, cons
 // Lagrange values u_j(s) -- is overwritten with zeros before it is released (the generators: s is a trapdoor element).
 void instance_map_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uint64_t *d_At, uint64_t *d_Bt, uint64_t *d_Ct,
                       uint64_t *d_Ht, uint64_t *d_Zt, hipStream_t st, bool wipe);
-// threads of a workgroup that holds one length-2^logn transform in LDS (decode, encode, keygen)
+// encoding.hip.  The body of rs_enc_decode / rs_enc_noise_budget at level K: d_enc [count][L][2][K][N_enc] over the first K
+// primes, the decoding multiplied by prod_{j >= K} Q_j mod q_i when K < ctx->K (modswitch.h).  d_rings == nullptr: budgets
+// only.  Takes the context's WsScope itself; returns RS_OK or throws (RS_ERR_NOISE: the guard).
+int decode_impl(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
+                rs_stream stream);
+// encoding.hip.  The wire format at level K.  deserialize_run: K_want == 0 accepts every level 1..ctx->K and reports it.
+size_t wire_size(const rs_ctx *ctx, int K, size_t count);
+void serialize_run(rs_ctx *ctx, int K, const uint64_t *d_enc, const uint8_t *h_empty, size_t count, void *h_buf, size_t buf_bytes,
+                   hipStream_t st);
+void deserialize_run(rs_ctx *ctx, int K_want, const void *h_buf, size_t buf_bytes, uint64_t *d_enc, uint8_t *h_empty, size_t capacity,
+                     size_t *h_count, int *K_found, hipStream_t st);
+// threads of a workgroup that holds one length-2^logn transform in LDS (decode, encode, keygen, mod switch)
 inline int enc_threads(int logn) { return (int)std::max(64, std::min(1024, (1 << logn) / 8)); }
 #if defined(__HIPCC__)
 // k-th output (1-based) of the splitmix64 stream `seed`: the sampler of rs_enc_encode and the generators (oracle/rs_oracle.c)

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "../../include/ringsnark_amd/modswitch.h"
 #include "../../include/ringsnark_amd/verify.h"
 #include "witness_eval.hpp"
 
@@ -479,16 +480,18 @@ static void vk_create(rs_ctx *ctx, int scheme, const rs_r1cs *cs, const uint64_t
   *out = reinterpret_cast<VK *>(vk);
 }
 
+// K_lvl: the level of the proof, d_proof [NE][L][2][K_lvl][N_enc] (ctx->K: an unswitched proof; modswitch.h)
 template <int SCHEME>
-static void verify(rs_ctx *ctx, const VkBase *cvk, const uint64_t *d_primary, const uint64_t *d_proof, const int *h_empty,
+static void verify(rs_ctx *ctx, int K_lvl, const VkBase *cvk, const uint64_t *d_primary, const uint64_t *d_proof, const int *h_empty,
                    rs_verify_report *h_report, hipStream_t st) {
   constexpr int NE = SCHEME == 0 ? 3 : 9, NC = SCHEME == 0 ? 1 : 6;
+  RS_REQUIRE(K_lvl >= 1 && K_lvl <= ctx->K, "level out of range: 1 <= K_lvl <= K");
   RS_REQUIRE(cvk && d_proof && h_report, "null argument");
   VkBase *vk = const_cast<VkBase *>(cvk);
   RS_REQUIRE(vk->ctx == ctx, "verification key of another context");
   RS_REQUIRE(vk->scheme == SCHEME, "verification key of the other scheme");
   RS_REQUIRE(d_primary || vk->n_inputs == 0, "null argument");
-  const size_t S = ctx->ring_words(), EW = ctx->enc_words();
+  const size_t S = ctx->ring_words(), EW = (size_t)ctx->L * 2 * K_lvl * ctx->N_enc;
   std::lock_guard<std::mutex> lk(vk->mu);
   // decode the runs of non-EMPTY elements (guard on: a spent budget ends the call as it ends the reference's verifier)
   for (int e = 0; e < NE;) {
@@ -499,8 +502,7 @@ static void verify(rs_ctx *ctx, const VkBase *cvk, const uint64_t *d_primary, co
     }
     int n = 1;
     while (e + n < NE && !(h_empty && h_empty[e + n])) n++;
-    const int status = rs_enc_decode(ctx, vk->sk, d_proof + (size_t)e * EW, (size_t)n, vk->dec + (size_t)e * S, (rs_stream)st);
-    if (status != RS_OK) throw Error(status, rs_last_error());
+    decode_impl(ctx, K_lvl, vk->sk, d_proof + (size_t)e * EW, (size_t)n, vk->dec + (size_t)e * S, nullptr, (rs_stream)st);
     e += n;
   }
   VerifyArgs a{};
@@ -572,14 +574,29 @@ void rs_rinocchio_vk_destroy(rs_rinocchio_vk *vk) { vk_free(const_cast<VkBase *>
 int rs_groth16_verify(rs_ctx *ctx, const rs_groth16_vk *vk, const uint64_t *d_primary, const uint64_t *d_proof, const int *h_empty,
                       rs_verify_report *h_report, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
-  verify<0>(ctx, vk_of(vk), d_primary, d_proof, h_empty, h_report, S(stream));
+  verify<0>(ctx, ctx->K, vk_of(vk), d_primary, d_proof, h_empty, h_report, S(stream));
   RS_API_END
 }
 
 int rs_rinocchio_verify(rs_ctx *ctx, const rs_rinocchio_vk *vk, const uint64_t *d_primary, const uint64_t *d_proof,
                         const int *h_empty, rs_verify_report *h_report, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
-  verify<1>(ctx, vk_of(vk), d_primary, d_proof, h_empty, h_report, S(stream));
+  verify<1>(ctx, ctx->K, vk_of(vk), d_primary, d_proof, h_empty, h_report, S(stream));
+  RS_API_END
+}
+
+// modswitch.h: the same verifiers on a proof of K_lvl primes -- only the decode differs
+int rs_groth16_verify_level(rs_ctx *ctx, const rs_groth16_vk *vk, int K_lvl, const uint64_t *d_primary, const uint64_t *d_proof,
+                            const int *h_empty, rs_verify_report *h_report, rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  verify<0>(ctx, K_lvl, vk_of(vk), d_primary, d_proof, h_empty, h_report, S(stream));
+  RS_API_END
+}
+
+int rs_rinocchio_verify_level(rs_ctx *ctx, const rs_rinocchio_vk *vk, int K_lvl, const uint64_t *d_primary, const uint64_t *d_proof,
+                              const int *h_empty, rs_verify_report *h_report, rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  verify<1>(ctx, K_lvl, vk_of(vk), d_primary, d_proof, h_empty, h_report, S(stream));
   RS_API_END
 }
 

@@ -317,24 +317,45 @@ class Device:
         _lib.check(self.lib.rs_rinocchio_vk_create(self.h, dcs.h, *[_ptr(x) for x in t], C.byref(h)))
         return DeviceVK(self, "rinocchio", h, dcs.n_inputs)
 
-    def _verify(self, fn, vk, scheme, n_elems, primary, proof, empty):
+    def _verify(self, fn, vk, scheme, n_elems, primary, proof, empty, level=None):
         assert vk.scheme == scheme and vk.h, "not a live %s verification key" % scheme
-        assert self._count(proof, self.enc_words) == n_elems
+        assert self._count(proof, self.level_words(level)) == n_elems
         assert vk.n_inputs == 0 or self._count(primary, self.ring_words) == vk.n_inputs
         em = None if empty is None else (C.c_int * n_elems)(*[int(e) for e in empty])
         rep = _lib.VerifyReport()
-        _lib.check(fn(self.h, vk.h, _ptr(primary) if vk.n_inputs else None, _ptr(proof), em, C.byref(rep), self.stream()))
+        lvl = () if level is None else (int(level),)
+        _lib.check(fn(self.h, vk.h, *lvl, _ptr(primary) if vk.n_inputs else None, _ptr(proof), em, C.byref(rep), self.stream()))
         return VerifyResult(bool(rep.accepted), int(rep.failed), tuple(int(x) for x in rep.n_bad), int(rep.first_check),
                             int(rep.first_limb), int(rep.first_slot), int(rep.lhs), int(rep.rhs))
 
-    def groth16_verify(self, vk, primary, proof, empty=None):
+    def groth16_verify(self, vk, primary, proof, empty=None, level=None):
         """groth16::verifier (groth16.tcc:117-170): primary [n_inputs][L][N], proof [3] encoding elements, empty: the flags
-        the prover returned.  A VerifyResult (truthy when accepted); RsError(RS_ERR_NOISE) for a proof past its noise budget."""
-        return self._verify(self.lib.rs_groth16_verify, vk, "groth16", 3, primary, proof, empty)
+        the prover returned.  A VerifyResult (truthy when accepted); RsError(RS_ERR_NOISE) for a proof past its noise budget.
+        level: the proof was switched to that many primes (enc_mod_switch; rs_groth16_verify_level)."""
+        fn = self.lib.rs_groth16_verify if level is None else self.lib.rs_groth16_verify_level
+        return self._verify(fn, vk, "groth16", 3, primary, proof, empty, level)
 
-    def rinocchio_verify(self, vk, primary, proof, empty=None):
-        """rinocchio::verifier (rinocchio.tcc:192-295): proof [9]; failed bit c = check c of verify.h (V', W', Y', H', L_beta, P)."""
-        return self._verify(self.lib.rs_rinocchio_verify, vk, "rinocchio", 9, primary, proof, empty)
+    def rinocchio_verify(self, vk, primary, proof, empty=None, level=None):
+        """rinocchio::verifier (rinocchio.tcc:192-295): proof [9]; failed bit c = check c of verify.h (V', W', Y', H', L_beta, P).
+        level: as in groth16_verify (rs_rinocchio_verify_level)."""
+        fn = self.lib.rs_rinocchio_verify if level is None else self.lib.rs_rinocchio_verify_level
+        return self._verify(fn, vk, "rinocchio", 9, primary, proof, empty, level)
+
+    # ---- mod-switched encodings (ringsnark_amd/modswitch.h): level = number of leading primes an encoding still has
+    def level_words(self, level=None):
+        """words of one encoding element of `level` primes (None: the context's K)"""
+        return self.enc_words if level is None else self.L * 2 * int(level) * self.N_enc
+
+    def enc_mod_switch(self, enc, K_out, K_in=None):
+        """EncodingElem::modswitch_inplace, K_in - K_out times (rs_enc_mod_switch): enc [..][L][2][K_in][N_enc] -> a new
+        tensor [..][L][2][K_out][N_enc], an encoding of the context with primes Q[:K_out].  K_in: read off enc's shape.
+        Needs no key.  The result decodes with enc_decode(sk, out, level=K_out)."""
+        K_in = int(enc.shape[-2]) if K_in is None else int(K_in)
+        assert enc.is_contiguous() and tuple(enc.shape[-4:]) == (self.L, 2, K_in, self.N_enc), tuple(enc.shape)
+        count = self._count(enc, self.level_words(K_in))
+        out = torch.empty(tuple(enc.shape[:-4]) + (self.L, 2, int(K_out), self.N_enc), dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.rs_enc_mod_switch(self.h, _ptr(enc), count, K_in, int(K_out), _ptr(out), self.stream()))
+        return out
 
     # ---- generators (ringsnark_amd/keygen.h)
     KEYGEN_SEED_STRIDE = 1 << 40  # seeds=<int>: vector v of a key encodes from seed + v * 2^40 (disjoint streams for any length < 2^40)
@@ -456,25 +477,48 @@ class Device:
         return pk
 
     # ---- 8(f) f4
-    def enc_serialize(self, enc, empty=None):
-        """Encoding elements (a proof, a key vector) -> bytes in the wire format of ringsnark_amd.h."""
+    def enc_serialize(self, enc, empty=None, level=None):
+        """Encoding elements (a proof, a key vector) -> bytes in the wire format of ringsnark_amd.h.
+        level: enc has that many primes (enc_mod_switch); the stream is what a context on Q[:level] writes."""
         import numpy as np
-        count = self._count(enc, self.enc_words)
-        size = self.lib.rs_enc_wire_size(self.h, count)
+        count = self._count(enc, self.level_words(level))
+        if level is None:
+            size = self.lib.rs_enc_wire_size(self.h, count)
+        else:
+            size = self.lib.rs_enc_wire_size_level(self.h, int(level), count)
+            if size == 0:
+                raise _lib.RsError(_lib.RS_ERR_INVALID, "level out of range: 1 <= K_lvl <= K")
         buf = np.empty(size, dtype=np.uint8)
         em = None
         if empty is not None:
             em = np.ascontiguousarray(empty, dtype=np.uint8)
             assert em.size == count
-        _lib.check(self.lib.rs_enc_serialize(self.h, _ptr(enc), None if em is None else em.ctypes.data_as(_lib.u8p), count,
-                                             buf.ctypes.data_as(C.c_void_p), size, self.stream()))
+        emp = None if em is None else em.ctypes.data_as(_lib.u8p)
+        if level is None:
+            _lib.check(self.lib.rs_enc_serialize(self.h, _ptr(enc), emp, count, buf.ctypes.data_as(C.c_void_p), size, self.stream()))
+        else:
+            _lib.check(self.lib.rs_enc_serialize_level(self.h, int(level), _ptr(enc), emp, count, buf.ctypes.data_as(C.c_void_p), size,
+                                                       self.stream()))
         return buf.tobytes()
 
-    def enc_deserialize(self, data):
-        """bytes -> (encodings [count][L][2][K][N_enc] on the device, empty flags).  Validates the stream."""
+    def enc_deserialize(self, data, level=None):
+        """bytes -> (encodings [count][L][2][K][N_enc] on the device, empty flags).  Validates the stream.
+        level: 0 accepts a stream of any level of this context, K_lvl only that one (rs_enc_deserialize_level); returns
+        (encodings [count][L][2][K_lvl][N_enc], empty flags, K_lvl)."""
         import numpy as np
         buf = np.frombuffer(data, dtype=np.uint8)
         cnt = C.c_size_t(0)
+        if level is not None:
+            found = C.c_int(0)
+            _lib.check(self.lib.rs_enc_deserialize_level(self.h, buf.ctypes.data_as(C.c_void_p), buf.size, None, None, 0, C.byref(cnt),
+                                                         C.byref(found), self.stream()))
+            if level and found.value != level:
+                raise _lib.RsError(_lib.RS_ERR_INVALID, "stream of level %d, expected level %d" % (found.value, level))
+            out = torch.empty((cnt.value, self.L, 2, found.value, self.N_enc), dtype=torch.int64, device=self.device)
+            em = np.zeros(cnt.value, dtype=np.uint8)
+            _lib.check(self.lib.rs_enc_deserialize_level(self.h, buf.ctypes.data_as(C.c_void_p), buf.size, _ptr(out),
+                                                         em.ctypes.data_as(_lib.u8p), cnt.value, C.byref(cnt), C.byref(found), self.stream()))
+            return out, em, found.value
         _lib.check(self.lib.rs_enc_deserialize(self.h, buf.ctypes.data_as(C.c_void_p), buf.size, None, None, 0, C.byref(cnt),
                                                self.stream()))
         out = self.enc_empty(cnt.value)
@@ -484,20 +528,28 @@ class Device:
         return out, em
 
     # ---- 8(f) f2 / f3
-    def enc_decode(self, sk, enc):
+    def enc_decode(self, sk, enc, level=None):
         """EncodingElem::decode (seal_ring.tcc:435-477): sk [K][N_enc] NTT form -> ring elements.  Raises
         RsError(RS_ERR_NOISE, "ciphertext #i has remaining noise budget 0 <= 0") like the reference's decoding_error
-        (seal_ring.tcc:446-454) when a ciphertext's invariant noise budget is spent."""
-        count = self._count(enc, self.enc_words)
+        (seal_ring.tcc:446-454) when a ciphertext's invariant noise budget is spent.
+        level: enc [..][L][2][level][N_enc] was switched to that many primes (rs_enc_decode_level)."""
+        count = self._count(enc, self.level_words(level))
         out = self.ring_empty(count) if enc.dim() > 4 else self.ring_empty()
-        _lib.check(self.lib.rs_enc_decode(self.h, _ptr(sk), _ptr(enc), count, _ptr(out), self.stream()))
+        if level is None:
+            _lib.check(self.lib.rs_enc_decode(self.h, _ptr(sk), _ptr(enc), count, _ptr(out), self.stream()))
+        else:
+            _lib.check(self.lib.rs_enc_decode_level(self.h, int(level), _ptr(sk), _ptr(enc), count, _ptr(out), self.stream()))
         return out
 
-    def enc_noise_budget(self, sk, enc):
-        """Decryptor::invariant_noise_budget of every ciphertext (bits; 0 = spent): int array [count][L]."""
-        count = self._count(enc, self.enc_words)
+    def enc_noise_budget(self, sk, enc, level=None):
+        """Decryptor::invariant_noise_budget of every ciphertext (bits; 0 = spent): int array [count][L].
+        level: as in enc_decode (rs_enc_noise_budget_level)."""
+        count = self._count(enc, self.level_words(level))
         out = (C.c_int * (count * self.L))()
-        _lib.check(self.lib.rs_enc_noise_budget(self.h, _ptr(sk), _ptr(enc), count, out, self.stream()))
+        if level is None:
+            _lib.check(self.lib.rs_enc_noise_budget(self.h, _ptr(sk), _ptr(enc), count, out, self.stream()))
+        else:
+            _lib.check(self.lib.rs_enc_noise_budget_level(self.h, int(level), _ptr(sk), _ptr(enc), count, out, self.stream()))
         return np.array(out, dtype=np.int64).reshape(count, self.L)
 
     def enc_encode(self, sk, rings, seed):
