@@ -145,8 +145,10 @@ __global__ void __launch_bounds__(256) broadcast_rows_kernel(const uint64_t *__r
 }
 // Term tile and chunk count of one msm_run (also what rs_prove_batch_bytes sizes the workspace by).
 // wide_blocks: the call runs mac_kernel_v3g (six groups per launch) where it would run mac_kernel_v3 in pairs.
-MsmGeometry msm_geometry(const rs_ctx *ctx, int n_crs, int n_groups, size_t Tmax, size_t crs_window, bool crs_on_host, bool seeded,
-                         bool wide_blocks) {
+MsmGeometry msm_geometry(const rs_ctx *ctx, const MsmKey &key, int n_groups, size_t Tmax, bool wide_blocks) {
+  const int n_crs = key.n;
+  const size_t crs_window = key.window;
+  const bool crs_on_host = key.on_host, seeded = key.pub_seeds != nullptr;
   const int L = ctx->L, K = ctx->K, n = ctx->N_enc;
   const size_t enc_words = ctx->enc_words();
   MsmGeometry G;
@@ -197,9 +199,13 @@ MsmGeometry msm_geometry(const rs_ctx *ctx, int n_crs, int n_groups, size_t Tmax
 // crs_window != 0: every CRS vector is stored as `crs_window` consecutive elements and logical
 // element t lives at index t % crs_window (tiled keys, see ringsnark_amd.h); tiles never straddle the wrap.
 template <class M>
-static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
-                          int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
-                          size_t crs_window, const MsmLin *lin, bool crs_on_host, const uint64_t *pub_seeds, bool wide_blocks) {
+static void msm_run_arith(rs_ctx *ctx, const MsmKey &key, const rs_msm_vec *vecs, int n_vecs, int n_groups, uint64_t *d_out,
+                          const uint64_t *const *addends, size_t *h_used, hipStream_t st, const MsmLin *lin, bool wide_blocks) {
+  const uint64_t *const *d_crs = key.vecs;
+  const int n_crs = key.n;
+  const size_t crs_len = key.len, crs_window = key.window;
+  const bool crs_on_host = key.on_host;
+  const uint64_t *pub_seeds = key.pub_seeds;
   using Lift = typename ArithOf<M>::Lift;
   constexpr bool FP = std::is_same<M, Mod>::value;
   RS_REQUIRE(n_crs >= 1 && n_crs <= 2, "n_crs must be 1 or 2");
@@ -312,7 +318,7 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   const bool seeded = pub_seeds != nullptr, staged = crs_on_host || seeded;
   const size_t key_words = seeded ? enc_words / 2 : enc_words;  // words of a stored element
   uint64_t *stage = nullptr, *land = nullptr;
-  const MsmGeometry geo = msm_geometry(ctx, n_crs, n_groups, Tmax, crs_window, crs_on_host, seeded, wide_blocks);
+  const MsmGeometry geo = msm_geometry(ctx, key, n_groups, Tmax, wide_blocks);
   const size_t tile_terms = geo.tile_terms, stage_words = geo.stage_words;
   if (staged) {
     stage = (uint64_t *)ws_get(ctx, WS_SMALL, (size_t)2 * n_crs * (stage_words + geo.land_words) * sizeof(uint64_t));
@@ -708,11 +714,10 @@ static void msm_run_arith(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, 
   }
 }
 
-void msm_run(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
-             int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
-             size_t crs_window, const MsmLin *lin, bool crs_on_host, const uint64_t *pub_seeds, bool wide_blocks) {
-  RS_DISPATCH_ARITH(ctx, (msm_run_arith<Mod>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host, pub_seeds, wide_blocks)),
-                    (msm_run_arith<ModI>(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, addends, h_used, st, crs_window, lin, crs_on_host, pub_seeds, wide_blocks)));
+void msm_run(rs_ctx *ctx, const MsmKey &key, const rs_msm_vec *vecs, int n_vecs, int n_groups, uint64_t *d_out,
+             const uint64_t *const *addends, size_t *h_used, hipStream_t st, const MsmLin *lin, bool wide_blocks) {
+  RS_DISPATCH_ARITH(ctx, (msm_run_arith<Mod>(ctx, key, vecs, n_vecs, n_groups, d_out, addends, h_used, st, lin, wide_blocks)),
+                    (msm_run_arith<ModI>(ctx, key, vecs, n_vecs, n_groups, d_out, addends, h_used, st, lin, wide_blocks)));
 }
 // can a call with linear-form vectors be served? (FP64 context on the wide plaintext kernel)
 bool msm_supports_lin(const rs_ctx *ctx) {
@@ -763,7 +768,7 @@ int rs_msm(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len,
   RS_API_BEGIN_CTX(ctx)
   RS_REQUIRE(ctx && d_crs && vecs && d_out && n_vecs >= 1, "null argument");
   WsScope ws_scope(ctx, S(stream));
-  msm_run(ctx, d_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, nullptr, h_used, S(stream), crs_window);
+  msm_run(ctx, MsmKey{d_crs, n_crs, crs_len, crs_window}, vecs, n_vecs, n_groups, d_out, nullptr, h_used, S(stream));
   RS_API_END
 }
 
@@ -772,7 +777,7 @@ int rs_msm_hostkey(rs_ctx *ctx, const uint64_t *const *h_crs, int n_crs, size_t 
   RS_API_BEGIN_CTX(ctx)
   RS_REQUIRE(ctx && h_crs && vecs && d_out && n_vecs >= 1, "null argument");
   WsScope ws_scope(ctx, S(stream));
-  msm_run(ctx, h_crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, nullptr, h_used, S(stream), crs_window, nullptr, true);
+  msm_run(ctx, MsmKey{h_crs, n_crs, crs_len, crs_window, true}, vecs, n_vecs, n_groups, d_out, nullptr, h_used, S(stream));
   RS_HIP(hipStreamSynchronize(S(stream)));  // the caller may release or rewrite the host key on return
   RS_API_END
 }
@@ -796,7 +801,7 @@ int rs_inner_product(rs_ctx *ctx, const uint64_t *d_encs, const uint64_t *d_ring
   WsScope ws_scope(ctx, S(stream));
   rs_msm_vec v{d_rings, h_kinds, T, 0};
   const uint64_t *crs[1] = {d_encs};
-  msm_run(ctx, crs, 1, T, &v, 1, 1, d_out, nullptr, h_used, S(stream), 0);
+  msm_run(ctx, MsmKey{crs, 1, T, 0}, &v, 1, 1, d_out, nullptr, h_used, S(stream));
   RS_API_END
 }
 
@@ -808,7 +813,7 @@ int rs_enc_mul_ring(rs_ctx *ctx, uint64_t *d_enc, const uint64_t *d_ring, size_t
   for (size_t k = 0; k < count; k++) {
     rs_msm_vec v{d_ring + k * ctx->ring_words(), nullptr, 1, 0};
     const uint64_t *crs[1] = {d_enc + k * ctx->enc_words()};
-    msm_run(ctx, crs, 1, 1, &v, 1, 1, tmp, nullptr, nullptr, S(stream), 0);
+    msm_run(ctx, MsmKey{crs, 1, 1, 0}, &v, 1, 1, tmp, nullptr, nullptr, S(stream));
     RS_HIP(hipMemcpyAsync(d_enc + k * ctx->enc_words(), tmp, ctx->enc_words() * sizeof(uint64_t),
                           hipMemcpyDeviceToDevice, S(stream)));
   }

@@ -146,10 +146,10 @@ enum WsSlot {
                      // msm_run with a host-resident or a seeded key: the two staging buffers of the key tiles (+ the two compact landing buffers of a host-resident seeded key).  vk_create calls rs_ring_inv and then io_eval_at: two scopes, one after the
                      // other.  normalised_len synchronises before it returns, so its three calls in one scope each take a dead pointer's place.  The provers reach msm_run
                      // after witness_run, which does not take this slot, and nothing else in a prover's scope does.
-  WS_PROVER_VECS,    // the provers (single and batched, batch.h): the witness map's output vectors, [batch][4m+1 | 5m+1] ring elements.  One prover per scope.
+  WS_PROVER_VECS,    // groth16_prove_members, rinocchio_prove_members: the witness map's output vectors, [B][prove_layout().vec_words] (prover.hip).  One prover per scope.
   WS_NOISE_BITS,     // decode_impl: significant bits of the noise per (element, limb)
-  WS_RINOCCHIO_OUT,  // rs_rinocchio_prove_kinds: the ten inner products and one temporary, [11] encoding elements; the batched provers: every
-                     // member's inner products before they are copied into the proofs ([4 batch], [2 (4 batch + 1) + batch + 1])
+  WS_PROVER_OUT,     // groth16_prove_members (batched only), rinocchio_prove_members: the members' inner products before they are copied into the
+                     // proofs, and Rinocchio's temporary: [prove_layout().out_elems] encoding elements (prover.hip)
   WS_PASS_A,         // launch_interp (W), launch_h (W1), bc_interp / bc_h (Xhat), bc2_interp / bc2_h (Wy), io_eval_run (tile products P): the first transform workspace.
                      // launch_interp has enqueued every reader of W when it returns and launch_h of the same witness_chunk takes the slot afresh (ws_get orders a
                      // reallocation after the stream's work); the bc / bc2 functions are what launch_interp and launch_h call INSTEAD of taking the slot themselves;
@@ -360,19 +360,25 @@ inline hipStream_t S(rs_stream s) { return (hipStream_t)s; }
 // ---- host functions that one unit defines and others call: declared here, and only here
 void launch_ntt(rs_ctx *ctx, const NttTable &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st);
 void launch_ntt_int(rs_ctx *ctx, const NttTableI &t, uint64_t *d_data, size_t batch, bool inverse, hipStream_t st);
+// The key side of an inner product: n key vectors of `len` elements each, and how they are stored.
+struct MsmKey {
+  const uint64_t *const *vecs;           // [n] device pointers (on_host: host pointers)
+  int n;                                 // 1 or 2
+  size_t len;                            // elements of every vector
+  size_t window;                         // != 0: `window` elements are stored and element t lives at index t % window (tiled keys, ringsnark_amd.h)
+  bool on_host = false;                  // host-resident: streamed tile by tile
+  const uint64_t *pub_seeds = nullptr;   // [n] public seeds: the vectors are compact, c0 only (seeded.h)
+};
 // msm.hip.  msm_run: the caller holds the context's WsScope
-void msm_run(rs_ctx *ctx, const uint64_t *const *d_crs, int n_crs, size_t crs_len, const rs_msm_vec *vecs, int n_vecs,
-             int n_groups, uint64_t *d_out, const uint64_t *const *addends, size_t *h_used, hipStream_t st,
-             size_t crs_window, const MsmLin *lin = nullptr, bool crs_on_host = false, const uint64_t *pub_seeds = nullptr,
-             bool wide_blocks = false);
+void msm_run(rs_ctx *ctx, const MsmKey &key, const rs_msm_vec *vecs, int n_vecs, int n_groups, uint64_t *d_out,
+             const uint64_t *const *addends, size_t *h_used, hipStream_t st, const MsmLin *lin = nullptr, bool wide_blocks = false);
 // term tile, chunk count and staging words of an msm_run with these arguments (wide_blocks: the batched provers, and every
 // call of more than six groups: mac_kernel_v3g where mac_kernel_v3 would run in pairs)
 struct MsmGeometry {
   size_t tile_terms = 0, stage_words = 0, land_words = 0;
   int n_chunks = 1;
 };
-MsmGeometry msm_geometry(const rs_ctx *ctx, int n_crs, int n_groups, size_t Tmax, size_t crs_window, bool crs_on_host, bool seeded,
-                         bool wide_blocks);
+MsmGeometry msm_geometry(const rs_ctx *ctx, const MsmKey &key, int n_groups, size_t Tmax, bool wide_blocks);
 bool msm_supports_lin(const rs_ctx *ctx);
 void batch_encode_run(rs_ctx *ctx, const uint64_t *d_rings, uint64_t *d_plain, size_t count, hipStream_t st);
 void enc_add_run(rs_ctx *ctx, uint64_t *dst, const uint64_t *x, const uint64_t *y, size_t count, hipStream_t st);
@@ -418,20 +424,17 @@ void expand_seeded_run(rs_ctx *ctx, const uint64_t *c0, bool linear, uint64_t pu
 // order of h_seeds; h_pub != nullptr: a seeded key.  Takes the context's WsScope itself.
 void keygen_run_scheme(int scheme, rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, const uint64_t *const *trap, const uint64_t *d_sk,
                        const uint64_t *h_seeds, const uint64_t *h_pub, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st);
-// prover.hip.  The bodies of rs_groth16_prove_kinds / rs_rinocchio_prove_kinds; pub != nullptr: the three vectors of pk are
-// compact and pub holds their public seeds (seeded.h).  They take the context's WsScope themselves.
-void groth16_prove_run(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *pub, const uint64_t *d_assignment,
-                       const uint8_t *h_assignment_kinds, uint64_t *d_proof, int *h_empty, hipStream_t st);
-void rinocchio_prove_run(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *pub, const uint64_t *d_assignment,
-                         const uint8_t *h_assignment_kinds, const uint64_t *d_d1, const uint64_t *d_d2, const uint64_t *d_d3,
-                         uint64_t *d_proof, int *h_empty, hipStream_t st);
-// prover.hip, batched (include/ringsnark_amd/batch.h): `batch` assignments against one key, one pass per key vector
-void groth16_prove_batch_run(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *pub, int batch,
-                             const uint64_t *const *d_assignments, const uint8_t *h_assignment_kinds, uint64_t *d_proofs, int *h_empty,
-                             hipStream_t st);
-void rinocchio_prove_batch_run(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *pub, int batch,
-                               const uint64_t *const *d_assignments, const uint8_t *h_assignment_kinds, const uint64_t *d_d123,
-                               uint64_t *d_proofs, int *h_empty, hipStream_t st);
+// prover.hip.  The body of every ringGroth16 / Rinocchio proving entry point: B assignments against one key, one pass per
+// key vector.  batched: false from the single-proof entry points (B == 1), true from those of include/ringsnark_amd/batch.h,
+// whatever B.  pub != nullptr: the three vectors of pk are compact and pub holds their public seeds (seeded.h).  h_kinds
+// [B][n_vars] or nullptr; d: d1, d2, d3 of member 0 (all null: not zero knowledge), member b's 3 b ring elements further.
+// They take the context's WsScope themselves.
+void groth16_prove_members(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *pub, int B,
+                           const uint64_t *const *d_assignments, const uint8_t *h_kinds, uint64_t *d_proofs, int *h_empty, bool batched,
+                           hipStream_t st);
+void rinocchio_prove_members(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *pub, int B,
+                             const uint64_t *const *d_assignments, const uint8_t *h_kinds, const uint64_t *const d[3], uint64_t *d_proofs,
+                             int *h_empty, bool batched, hipStream_t st);
 // witness_plan.hip
 const uint64_t *witness_Z_rows(rs_ctx *ctx, size_t m);
 void witness_plans_destroy(rs_ctx *ctx);  // every plan of the context (rs_ctx_destroy)

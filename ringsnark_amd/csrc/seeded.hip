@@ -78,6 +78,16 @@ void expand_seeded_run(rs_ctx *ctx, const uint64_t *c0, bool linear, uint64_t pu
   RS_HIP(hipGetLastError());
 }
 
+// A seeded key in the full key's struct, as the provers' bodies take it beside pk->pub_seeds: the same vectors, compact
+static rs_groth16_pk full_format(const rs_groth16_pk_seeded *pk) {
+  RS_REQUIRE(pk != nullptr, "null argument");
+  return {pk->s_pows, pk->delta_ts, pk->delta_mid, pk->d_alpha, pk->d_beta, pk->window, pk->host_key};
+}
+static rs_rinocchio_pk full_format(const rs_rinocchio_pk_seeded *pk) {
+  RS_REQUIRE(pk != nullptr, "null argument");
+  return {pk->s_pows, pk->alpha_s_pows, pk->beta_prods, pk->d_beta_rv_ts, pk->d_beta_rw_ts, pk->d_beta_ry_ts, pk->window, pk->host_key};
+}
+
 }  // namespace rs
 
 using namespace rs;
@@ -123,8 +133,8 @@ int rs_msm_seeded(rs_ctx *ctx, const uint64_t *const *crs, const uint64_t *h_pub
   RS_REQUIRE(crs && h_pub_seeds && vecs && d_out && n_vecs >= 1, "null argument");
   RS_REQUIRE(crs_on_host == 0 || crs_on_host == 1, "crs_on_host must be 0 or 1");
   WsScope ws_scope(ctx, S(stream));
-  msm_run(ctx, crs, n_crs, crs_len, vecs, n_vecs, n_groups, d_out, nullptr, h_used, S(stream), crs_window, nullptr, crs_on_host != 0,
-          h_pub_seeds);
+  msm_run(ctx, MsmKey{crs, n_crs, crs_len, crs_window, crs_on_host != 0, h_pub_seeds}, vecs, n_vecs, n_groups, d_out, nullptr, h_used,
+          S(stream));
   if (crs_on_host) RS_HIP(hipStreamSynchronize(S(stream)));  // the caller may release or rewrite the host key on return
   RS_API_END
 }
@@ -132,9 +142,8 @@ int rs_msm_seeded(rs_ctx *ctx, const uint64_t *const *crs, const uint64_t *h_pub
 int rs_groth16_prove_seeded(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk_seeded *pk, const uint64_t *d_assignment,
                             const uint8_t *h_assignment_kinds, uint64_t *d_proof, int *h_empty, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
-  RS_REQUIRE(pk != nullptr, "null argument");
-  const rs_groth16_pk full{pk->s_pows, pk->delta_ts, pk->delta_mid, pk->d_alpha, pk->d_beta, pk->window, pk->host_key};
-  groth16_prove_run(ctx, cs, &full, pk->pub_seeds, d_assignment, h_assignment_kinds, d_proof, h_empty, S(stream));
+  const rs_groth16_pk full = full_format(pk);
+  groth16_prove_members(ctx, cs, &full, pk->pub_seeds, 1, &d_assignment, h_assignment_kinds, d_proof, h_empty, false, S(stream));
   RS_API_END
 }
 
@@ -142,10 +151,9 @@ int rs_rinocchio_prove_seeded(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio
                               const uint8_t *h_assignment_kinds, const uint64_t *d_d1, const uint64_t *d_d2, const uint64_t *d_d3,
                               uint64_t *d_proof, int *h_empty, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
-  RS_REQUIRE(pk != nullptr, "null argument");
-  const rs_rinocchio_pk full{pk->s_pows, pk->alpha_s_pows, pk->beta_prods, pk->d_beta_rv_ts, pk->d_beta_rw_ts, pk->d_beta_ry_ts,
-                             pk->window, pk->host_key};
-  rinocchio_prove_run(ctx, cs, &full, pk->pub_seeds, d_assignment, h_assignment_kinds, d_d1, d_d2, d_d3, d_proof, h_empty, S(stream));
+  const rs_rinocchio_pk full = full_format(pk);
+  const uint64_t *d[3] = {d_d1, d_d2, d_d3};
+  rinocchio_prove_members(ctx, cs, &full, pk->pub_seeds, 1, &d_assignment, h_assignment_kinds, d, d_proof, h_empty, false, S(stream));
   RS_API_END
 }
 
@@ -153,9 +161,8 @@ int rs_groth16_prove_batch_seeded(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth
                                   const uint64_t *const *d_assignments, const uint8_t *h_assignment_kinds, uint64_t *d_proofs,
                                   int *h_empty, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
-  RS_REQUIRE(pk != nullptr, "null argument");
-  const rs_groth16_pk full{pk->s_pows, pk->delta_ts, pk->delta_mid, pk->d_alpha, pk->d_beta, pk->window, pk->host_key};
-  groth16_prove_batch_run(ctx, cs, &full, pk->pub_seeds, batch, d_assignments, h_assignment_kinds, d_proofs, h_empty, S(stream));
+  const rs_groth16_pk full = full_format(pk);
+  groth16_prove_members(ctx, cs, &full, pk->pub_seeds, batch, d_assignments, h_assignment_kinds, d_proofs, h_empty, true, S(stream));
   RS_API_END
 }
 
@@ -163,11 +170,10 @@ int rs_rinocchio_prove_batch_seeded(rs_ctx *ctx, const rs_r1cs *cs, const rs_rin
                                     const uint64_t *const *d_assignments, const uint8_t *h_assignment_kinds, const uint64_t *d_d123,
                                     uint64_t *d_proofs, int *h_empty, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
-  RS_REQUIRE(pk != nullptr, "null argument");
-  const rs_rinocchio_pk full{pk->s_pows, pk->alpha_s_pows, pk->beta_prods, pk->d_beta_rv_ts, pk->d_beta_rw_ts, pk->d_beta_ry_ts,
-                             pk->window, pk->host_key};
-  rinocchio_prove_batch_run(ctx, cs, &full, pk->pub_seeds, batch, d_assignments, h_assignment_kinds, d_d123, d_proofs, h_empty,
-                            S(stream));
+  const rs_rinocchio_pk full = full_format(pk);
+  const size_t rw = ctx->ring_words();
+  const uint64_t *d[3] = {d_d123, d_d123 ? d_d123 + rw : nullptr, d_d123 ? d_d123 + 2 * rw : nullptr};
+  rinocchio_prove_members(ctx, cs, &full, pk->pub_seeds, batch, d_assignments, h_assignment_kinds, d, d_proofs, h_empty, true, S(stream));
   RS_API_END
 }
 

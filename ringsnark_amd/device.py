@@ -765,21 +765,11 @@ class Device:
         violated constraint, limb and slot, for an assignment that does not satisfy the system."""
         if check:
             self._require_satisfied(dcs, assignment)
-        host_key = isinstance(pk["s_pows"], HostWords)
-        addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
-        assert all(isinstance(pk[k], HostWords) == host_key for k in ("s_pows", "delta_ts") + (("delta_mid",) if pk.get("delta_mid") is not None else ()))
+        s, seeded = self._groth16_key(pk, window)
         proof = self.enc_empty(3)
         empty = (C.c_int * 3)()
         keep, kp = self._kinds(kinds, dcs.n_vars)
-        if "pub_seeds" in pk:  # a seeded key (groth16_keygen(seeded=True)): compact vectors
-            s = _lib.Groth16PKSeeded(addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk.get("delta_mid")),
-                                     (C.c_uint64 * 3)(*self._keygen_seeds(list(pk["pub_seeds"][:3]), 3)), pk["alpha"].data_ptr(),
-                                     pk["beta"].data_ptr(), window, 1 if host_key else 0)
-            prove = self.lib.rs_groth16_prove_seeded
-        else:
-            s = _lib.Groth16PK(addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk.get("delta_mid")),
-                               pk["alpha"].data_ptr(), pk["beta"].data_ptr(), window, 1 if host_key else 0)
-            prove = self.lib.rs_groth16_prove_kinds
+        prove = self.lib.rs_groth16_prove_seeded if seeded else self.lib.rs_groth16_prove_kinds
         _lib.check(prove(self.h, dcs.h, C.byref(s), _ptr(assignment), kp, _ptr(proof), empty if want_empty else None, self.stream()))
         return proof, [int(e) for e in empty]
 
@@ -787,26 +777,17 @@ class Device:
         """check: as in groth16_prove (the reference asserts satisfaction at r1cs_to_qrp.tcc:156)."""
         if check:
             self._require_satisfied(dcs, assignment)
-        host_key = isinstance(pk.get("s_pows"), HostWords)
-        g = lambda k: None if pk.get(k) is None else (pk[k].ptr if isinstance(pk[k], HostWords) else pk[k].data_ptr())
+        s, seeded = self._rinocchio_key(pk, window)
         proof = self.enc_empty(9)
         empty = (C.c_int * 9)()
         keep, kp = self._kinds(kinds, dcs.n_vars)
-        if "pub_seeds" in pk:  # a seeded key (rinocchio_keygen(seeded=True)): compact vectors
-            s = _lib.RinocchioPKSeeded(g("s_pows"), g("alpha_s_pows"), g("beta_prods"),
-                                       (C.c_uint64 * 3)(*self._keygen_seeds(list(pk["pub_seeds"][:3]), 3)), g("beta_rv_ts"), g("beta_rw_ts"),
-                                       g("beta_ry_ts"), window, 1 if host_key else 0)
-            prove = self.lib.rs_rinocchio_prove_seeded
-        else:
-            s = _lib.RinocchioPK(g("s_pows"), g("alpha_s_pows"), g("beta_prods"), g("beta_rv_ts"), g("beta_rw_ts"), g("beta_ry_ts"),
-                                 window, 1 if host_key else 0)
-            prove = self.lib.rs_rinocchio_prove_kinds
+        prove = self.lib.rs_rinocchio_prove_seeded if seeded else self.lib.rs_rinocchio_prove_kinds
         _lib.check(prove(self.h, dcs.h, C.byref(s), _ptr(assignment), kp, _ptr(d1), _ptr(d2), _ptr(d3), _ptr(proof), empty, self.stream()))
         return proof, [int(e) for e in empty]
 
     # ---- batched proving (include/ringsnark_amd/batch.h)
     def _groth16_key(self, pk, window):
-        """(key struct, seeded) of a key dictionary, dispatched as groth16_prove does"""
+        """(key struct, seeded) of a key dictionary; seeded: it has "pub_seeds" (groth16_keygen(seeded=True)) and compact vectors"""
         host_key = isinstance(pk["s_pows"], HostWords)
         addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
         assert all(isinstance(pk[k], HostWords) == host_key for k in ("s_pows", "delta_ts") + (("delta_mid",) if pk.get("delta_mid") is not None else ()))
