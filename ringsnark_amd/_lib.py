@@ -72,6 +72,11 @@ class VerifyReport(C.Structure):
                 ("first_limb", C.c_uint32), ("first_slot", C.c_uint32), ("lhs", C.c_uint64), ("rhs", C.c_uint64)]
 
 
+class BitsReport(C.Structure):
+    _fields_ = [("n_bad", C.c_uint64), ("first_elem", C.c_uint64), ("first_limb", C.c_uint32), ("first_slot", C.c_uint32),
+                ("word", C.c_uint64), ("value", C.c_uint64)]
+
+
 class Groth16KeyOut(C.Structure):
     _fields_ = [("s_pows", vp), ("delta_ts", vp), ("delta_mid", vp), ("d_alpha", vp), ("d_beta", vp), ("host_key", C.c_int),
                 ("tile", C.c_size_t)]
@@ -233,6 +238,10 @@ MODSWITCH_SIGNATURES = {  # every function of include/ringsnark_amd/modswitch.h
     "rs_rinocchio_verify_level": (C.c_int, [vp, vp, C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(VerifyReport), vp]),
 }
 
+BITS_SIGNATURES = {  # every function of include/ringsnark_amd/bits.h
+    "rs_ring_bit_decompose": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(BitsReport), vp]),
+}
+
 _lib = None
 
 
@@ -247,7 +256,7 @@ def load():
             "the HIP library is the only implementation, there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **SOLVE_SIGNATURES, **VERIFY_SIGNATURES,
-                              **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES, **MODSWITCH_SIGNATURES}.items():
+                              **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES, **MODSWITCH_SIGNATURES, **BITS_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from .params import RingParams
-from .r1cs import R1CS, SOLVE_BLOCKED, R1csCheck, SolveInfo, given_mask
+from .r1cs import R1CS, SOLVE_BLOCKED, R1csCheck, SolveInfo, given_mask, plaintext_check_layout
 
 
 def to_device(a: np.ndarray, device) -> torch.Tensor:
@@ -140,6 +140,14 @@ class VerifyResult(collections.namedtuple("VerifyResult", "accepted failed n_bad
 
     def __bool__(self):
         return bool(self.accepted)
+
+
+class BitsResult(collections.namedtuple("BitsResult", "n_bad first_elem first_limb first_slot word value")):
+    """rs_bits_report (ringsnark_amd/bits.h), field for field; true when no position is bad."""
+    __slots__ = ()
+
+    def __bool__(self):
+        return self.n_bad == 0
 
 
 class DeviceVK:
@@ -451,18 +459,22 @@ class Device:
             _lib.check(self.lib.rs_groth16_keygen(*args, C.byref(out), self.stream()))
         return pk
 
-    def rinocchio_keygen(self, dcs, vk, seeds=None, host=False, tile=0, seeded=False, pub_seeds=None, allow_shared_seeds=False):
+    def rinocchio_keygen(self, dcs, vk, seeds=None, host=False, tile=0, seeded=False, pub_seeds=None, allow_shared_seeds=False,
+                         into=None):
         """rinocchio::generator (rinocchio.tcc:5-72): the dict rinocchio_prove accepts, from the dict rinocchio_vk takes.
         seeds: s_pows, alpha_s_pows, beta_prods, beta_rv_ts, beta_rw_ts, beta_ry_ts.  seeded, pub_seeds, allow_shared_seeds:
-        as in groth16_keygen (six public seeds)."""
+        as in groth16_keygen (six public seeds).  into: a key this call returned for the same system, `host` and `seeded`,
+        whose buffers are written again instead of new ones (a host-resident key is tens of GiB of page-locked memory)."""
         t = {k: self._vk_part(vk[k]) for k in ("s", "alpha", "beta", "r_v", "r_w", "r_y", "sk")}
         m, n_aux = dcs.m, dcs.n_vars - dcs.n_inputs
         if seeded:
             pub, pub_words = self._public_seeds(seeds, pub_seeds, [m + 1, m + 1, n_aux, 1, 1, 1], allow_shared_seeds)
         self.sync()
-        pk = dict(s_pows=self._key_vector(m + 1, host, seeded), alpha_s_pows=self._key_vector(m + 1, host, seeded),
-                  beta_prods=self._key_vector(n_aux, host, seeded) if n_aux else None, beta_rv_ts=self.enc_empty(),
-                  beta_rw_ts=self.enc_empty(), beta_ry_ts=self.enc_empty())
+        pk = into if into is not None else dict(
+            s_pows=self._key_vector(m + 1, host, seeded), alpha_s_pows=self._key_vector(m + 1, host, seeded),
+            beta_prods=self._key_vector(n_aux, host, seeded) if n_aux else None, beta_rv_ts=self.enc_empty(),
+            beta_rw_ts=self.enc_empty(), beta_ry_ts=self.enc_empty())
+        assert isinstance(pk["s_pows"], HostWords) == bool(host) and ("pub_seeds" in pk) == bool(seeded and into is not None)
         addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
         members = (addr(pk["s_pows"]), addr(pk["alpha_s_pows"]), addr(pk["beta_prods"]), pk["beta_rv_ts"].data_ptr(),
                    pk["beta_rw_ts"].data_ptr(), pk["beta_ry_ts"].data_ptr(), 1 if host else 0, tile)
@@ -653,6 +665,39 @@ class Device:
         stats = _lib.SolveStats()
         _lib.check(self.lib.rs_r1cs_solve(self.h, plan.h, _ptr(assignment), SOLVE_MODES[mode], C.byref(stats), self.stream()))
         return SolveStats(int(stats.level_launches), int(stats.walk_launches))
+
+    def ring_bit_decompose(self, x, nbits, out=None, x_stride=1, bits_stride=None, want_report=True):
+        """The bit rows of ring elements whose slots hold one integer below 2^nbits in every limb (rs_ring_bit_decompose).
+        x: a tensor whose element e is the ring element at x_stride * e ring elements (x_stride = 1: [count][L][N]); bit k
+        of element e is written to ring element e * bits_stride + k of `out` (default bits_stride = nbits; out = None: a
+        new [count][nbits][L][N]).  x and out may be views of one assignment as long as no x row is a bit row.
+        Returns (out, BitsResult), or (out, None) with want_report=False: enqueued only, nothing is downloaded."""
+        bits_stride = nbits if bits_stride is None else bits_stride
+        assert x_stride >= 1, "x_stride must be at least 1"
+        count = (self._count(x, self.ring_words) - 1) // x_stride + 1 if x.numel() else 0
+        if out is None:
+            assert bits_stride == nbits, "a strided output needs `out`"
+            out = self.ring_empty(count, nbits)
+        elif count:
+            need = (count - 1) * bits_stride + nbits
+            assert self._count(out, self.ring_words) >= need, "out holds fewer than (count - 1) * bits_stride + nbits ring elements"
+        rep = _lib.BitsReport()
+        _lib.check(self.lib.rs_ring_bit_decompose(self.h, _ptr(x), x_stride, count, nbits, _ptr(out), bits_stride,
+                                                  C.byref(rep) if want_report else None, self.stream()))
+        if not want_report:
+            return out, None
+        return out, BitsResult(*[int(getattr(rep, k)) for k, _ in _lib.BitsReport._fields_])
+
+    def plaintext_check_fill_bits(self, assignment, cs_or_logT, count, constants=False, want_report=True):
+        """Fills the bit rows of a plaintext_check_r1cs assignment [n_vars][L][N] in place from its x rows (block p: rows
+        b_0 .. b_{logT-1}, x): one strided rs_ring_bit_decompose, x_stride = bits_stride = logT + 1.  The circuit is given
+        as the R1CS itself or as logT and `constants`.  Returns the report."""
+        logT, first = plaintext_check_layout(cs_or_logT, count, constants)
+        rows = assignment.view(-1, self.L, self.N)
+        assert rows.shape[0] == first + count * (logT + 1), "not an assignment of %d blocks of logT = %d" % (count, logT)
+        _, rep = self.ring_bit_decompose(rows[first + logT:], logT, out=rows[first:], x_stride=logT + 1, bits_stride=logT + 1,
+                                         want_report=want_report)
+        return rep
 
     def _require_satisfied(self, dcs, assignment):
         r = self.r1cs_check(dcs, assignment)

@@ -397,6 +397,115 @@ def logreg_assignment(num_features, inputs, ring_mul, ring_add, ring_mul_scalar)
     return _cat(parts)
 
 
+@dataclass
+class BitsReport:
+    """What a bit decomposition reports (rs_bits_report of ringsnark_amd/bits.h, field for field)."""
+    n_bad: int  # bad ring-layout positions (element, limb, slot)
+    first_elem: int  # lowest element with a bad position, then the lowest limb*N + slot in it; all 0 when there is none
+    first_limb: int
+    first_slot: int
+    word: int  # the word at that position
+    value: int  # the limb-0 word of that slot
+
+    @property
+    def clean(self):
+        return self.n_bad == 0
+
+
+def max_nbits(q: List[int]) -> int:
+    """min_i floor(log2 q_i): every value below 2^max_nbits is a canonical residue in every limb."""
+    return min(int(p).bit_length() - 1 for p in q)
+
+
+def bit_decompose(x, nbits: int, q: List[int]):
+    """The host mirror of rs_ring_bit_decompose (ringsnark_amd/bits.h), exact.  x: uint64 [count][L][N] (or one element
+    [L][N]).  Per (element, slot), with v the limb-0 word: bits[e, k, :, slot] = (v >> k) & 1 in every limb, k < nbits.
+    A position (element, limb i, slot) is bad when i == 0 and v >= 2^nbits, or i > 0 and the limb-i word differs from v.
+    Returns (bits uint64 [count][nbits][L][N] (or [nbits][L][N]), BitsReport)."""
+    x = np.asarray(x, dtype=np.uint64)
+    single = x.ndim == 2
+    xs = x[None] if single else x
+    assert xs.ndim == 3 and xs.shape[1] == len(q), xs.shape
+    assert 1 <= nbits <= max_nbits(q), "nbits must be between 1 and min_i floor(log2 q_i) = %d" % max_nbits(q)
+    count, L, N = xs.shape
+    v = xs[:, 0]
+    ks = np.arange(nbits, dtype=np.uint64).reshape(1, nbits, 1, 1)
+    bits = np.broadcast_to((v[:, None, None, :] >> ks) & np.uint64(1), (count, nbits, L, N)).copy()
+    bad = xs != v[:, None, :]
+    bad[:, 0] = (v >> np.uint64(nbits)) != 0
+    n_bad = int(bad.sum())
+    if n_bad == 0:
+        rep = BitsReport(0, 0, 0, 0, 0, 0)
+    else:
+        key = int(np.argmax(bad.reshape(-1)))
+        e, idx = divmod(key, L * N)
+        limb, slot = divmod(idx, N)
+        rep = BitsReport(n_bad, e, limb, slot, int(xs[e, limb, slot]), int(xs[e, 0, slot]))
+    return (bits[0] if single else bits), rep
+
+
+def plaintext_check_r1cs(q: List[int], logT: int, count: int = 1, constants: bool = False, n_inputs: Optional[int] = None) -> R1CS:
+    """The range check by bit decomposition of the reference's examples/example_plaintext_check_SEAL.cpp:36-54 and
+    benchmarks/bench_plaintext_check_SEAL.cpp:49-68, `count` times: count * (logT + 1) constraints.
+
+    constants=False (the default): variable 1 is a public wire `one` (n_inputs = 1; the verifier supplies one = 1), and
+    block p follows as b_{p,0} .. b_{p,logT-1}, x_p (variables 2 + p (logT+1) + i, 1-based):
+        b_{p,i} * (one - b_{p,i}) = 0   for i < logT,      x_p * one = sum_i 2^i b_{p,i}.
+    constants=True: the reference's file verbatim -- the constant one stands where `one` stood and no extra variable
+    exists (block p: variables 1 + p (logT+1) + i): vars[i] * (1 - vars[i]) = 0, vars[logT] * 1 = sum (1 << i) vars[i].
+    n_inputs defaults to 1 (the example, example_plaintext_check_SEAL.cpp:44); n_inputs = logT is the benchmark
+    (bench_plaintext_check_SEAL.cpp:58).  Coefficients are the true 2^i mod q_l.  The benchmark's `(1 << i)`
+    (bench_plaintext_check_SEAL.cpp:65, logT = 32) is evaluated in `int` and is NOT 2^31 at i = 31 (a negative value
+    where the shift is defined at all); this generator does not reproduce that.
+    The reference's own verifier REJECTS the constants=True form: its witness map counts terms on the constant one in
+    both its io and its mid pass (r1cs_to_qrp.tcc:175-201), so with a satisfied assignment rinocchio::verifier fails
+    exactly `L_beta = L` and `P = H Z(s)` (rinocchio.tcc:283-293).  The same circuit on the public wire `one` is accepted,
+    which is why it is the default and what the end-to-end tests use."""
+    assert logT >= 1 and count >= 1
+    w = logT + 1
+    rows = {"a": [], "b": [], "c": []}
+    one = 0 if constants else 1
+    first = 1 if constants else 2
+    for p in range(count):
+        b = [first + p * w + i for i in range(logT)]
+        x = first + p * w + logT
+        for i in range(logT):
+            rows["a"].append([(b[i], 1)])
+            rows["b"].append([(one, 1), (b[i], -1)])
+            rows["c"].append([])
+        rows["a"].append([(x, 1)])
+        rows["b"].append([(one, 1)])
+        rows["c"].append([(b[i], 1 << i) for i in range(logT)])
+    n_vars = count * w + (0 if constants else 1)
+    return from_rows(count * w, n_vars, 1 if n_inputs is None else n_inputs, rows, q)
+
+
+def plaintext_check_layout(cs_or_logT, count: int, constants: bool = False):
+    """(logT, first_bit_row): block p of a plaintext_check_r1cs assignment is rows first_bit_row + p (logT+1) ..,
+    b_0 .. b_{logT-1} then x.  From the circuit itself (count blocks) or from logT and `constants`."""
+    if isinstance(cs_or_logT, R1CS):
+        cs = cs_or_logT
+        assert cs.m % count == 0 and cs.n_vars - cs.m in (0, 1), "not a plaintext_check_r1cs of %d blocks" % count
+        return cs.m // count - 1, cs.n_vars - cs.m
+    return int(cs_or_logT), 0 if constants else 1
+
+
+def plaintext_check_assignment(cs_or_logT, xs, q: List[int], constants: bool = False) -> np.ndarray:
+    """The host assignment [n_vars][L][N] of plaintext_check_r1cs from the values xs [count][L][N] (every slot one
+    integer below 2^logT, the same word in every limb): `one` (unless constants), then per block the bit rows and x."""
+    xs = np.asarray(xs, dtype=np.uint64)
+    assert xs.ndim == 3 and xs.shape[1] == len(q), xs.shape
+    count = xs.shape[0]
+    logT, first = plaintext_check_layout(cs_or_logT, count, constants)
+    bits, _ = bit_decompose(xs, logT, q)
+    asg = np.empty((first + count * (logT + 1),) + xs.shape[1:], dtype=np.uint64)
+    asg[:first] = 1
+    blocks = asg[first:].reshape((count, logT + 1) + xs.shape[1:])
+    blocks[:, :logT] = bits
+    blocks[:, logT] = xs
+    return asg
+
+
 def _cat(parts):
     if isinstance(parts[0], np.ndarray):
         return np.ascontiguousarray(np.concatenate(parts))
