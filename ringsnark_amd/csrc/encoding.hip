@@ -13,49 +13,63 @@
 // error), which is all the parity tests can pin.  Any valid BGV ciphertext exercises the prover.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "ntt_core.hpp"
 #include "rs_internal.hpp"
 
 namespace rs {
 
+// The kernels of this unit are written once on the vocabulary of intmod.hpp and instantiated for both arithmetics:
+// M = Mod (exact FP64, lazy values) or ModI (contexts with a modulus >= 2^50: canonical residues, table constants in
+// Montgomery form; mulmod = data x constant, mulmod_dd = data x data).
+
 // ---- decode ----------------------------------------------------------------------------------
-// v_j = iNTT_{Q_j}(c0 + c1 * s), canonical doubles.  grid (count * L, K)
+// v_j = iNTT_{Q_j}(c0 + c1 * s), canonical values.  grid (count * L, K)
+template <class M>
 __global__ void __launch_bounds__(1024)
-decrypt_dot_kernel(const uint64_t *__restrict__ enc, const uint64_t *__restrict__ sk, double *__restrict__ V, int K, int logn,
-                   const NttTable *__restrict__ coeff_tabs) {
+decrypt_dot_kernel(const uint64_t *__restrict__ enc, const uint64_t *__restrict__ sk, typename ArithOf<M>::T *__restrict__ V, int K, int logn,
+                   const NttTableT<typename ArithOf<M>::T, M> *__restrict__ coeff_tabs) {
+  using T = typename ArithOf<M>::T;
+  constexpr bool FP = std::is_same<M, Mod>::value;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *s = reinterpret_cast<double *>(smem);
+  T *s = reinterpret_cast<T *>(smem);
   const int n = 1 << logn;
   const size_t el = blockIdx.x;  // (element, limb)
   const int j = blockIdx.y;
-  const NttTable tab = coeff_tabs[j];
-  const Mod mod = tab.mod;
+  const NttTableT<T, M> tab = coeff_tabs[j];
+  const M mod = tab.mod;
   const uint64_t *c0 = enc + (el * 2 * K + j) * (size_t)n, *c1 = c0 + (size_t)K * n;
   const uint64_t *sj = sk + (size_t)j * n;
   for (int x = threadIdx.x; x < n; x += blockDim.x)
-    s[pidx(x)] = from_u64(c0[x]) + mulmod(from_u64(c1[x]), from_u64(sj[x]), mod);
+    s[pidx(x)] = addm(from_res<T>(c0[x]), mulmod_dd(from_res<T>(c1[x]), from_res<T>(sj[x]), mod), mod);
   __syncthreads();
-  lds_ntt_inv(s, logn, tab.d_itw, 1, mod, tab.inv_red_mask);
-  double *dst = V + (el * K + j) * (size_t)n;
+  lds_ntt_inv(s, logn, tab.d_itw, 1, mod, FP ? tab.inv_red_mask : 0u);
+  T *dst = V + (el * K + j) * (size_t)n;
   for (int x = threadIdx.x; x < n; x += blockDim.x) dst[x] = canon(mulmod(reduce(s[pidx(x)], mod), tab.ninv, mod), mod);
 }
 
 // Constants of the CRT composition (SEAL Decryptor::bgv_decrypt composes to the centred
 // representative mod Q before reducing mod t): Garner mixed-radix digits, no big integers.
-struct CrtConsts {
+// What a kernel multiplies by is a table constant of the arithmetic (HostArith<M>::konst: balanced double / Montgomery
+// form); what it adds, subtracts or compares is a plain canonical value (HostArith<M>::plain).
+template <class M>
+struct CrtConstsT {
+  using T = typename ArithOf<M>::T;
   int K;
-  Mod Qmod[RS_MAX_K];
-  double half[RS_MAX_K];                  // mixed-radix digits of floor(Q/2)
-  double prod_inv[RS_MAX_K];              // (prod_{i<k} Q_i)^-1 mod Q_k
-  double Qi_mod_Qk[RS_MAX_K][RS_MAX_K];   // [i][k] = Q_i mod Q_k
+  M Qmod[RS_MAX_K];
+  T half[RS_MAX_K];                 // mixed-radix digits of floor(Q/2), plain
+  T prod_inv[RS_MAX_K];             // (prod_{i<k} Q_i)^-1 mod Q_k, constant
+  T Qi_mod_Qk[RS_MAX_K][RS_MAX_K];  // [i][k] = Q_i mod Q_k, constant
 };
-struct CrtLimb {
-  Mod tmod;
-  double Qk_mod_t[RS_MAX_K];
-  double Q_mod_t;
-  double F;   // level factor prod_{j >= K} Q_j mod t of a decode below the context's level (modswitch.h)
-  int scale;  // 0: the context's own level, F = 1 and no product is made
+template <class M>
+struct CrtLimbT {
+  using T = typename ArithOf<M>::T;
+  M tmod;
+  T Qk_mod_t[RS_MAX_K];  // constant
+  T Q_mod_t;             // plain: the canonical residue in both arithmetics (it is subtracted, and the result reduced)
+  T F;                   // constant: level factor prod_{j >= K} Q_j mod t of a decode below the context's level (modswitch.h)
+  int scale;             // 0: the context's own level, F = 1 and no product is made
 };
 
 // ---- the noise guard of EncodingElem::decode (seal_ring.tcc:443-454) ----------------------------------------------
@@ -85,33 +99,37 @@ __device__ __forceinline__ int magnitude_bits(const T *d, bool upper, const T *Q
 }
 
 // centred CRT composition mod t, forward NTT mod t, slot gather.  grid (count * L)
+template <class M>
 __global__ void __launch_bounds__(1024)
-crt_decode_kernel(const double *__restrict__ V, uint64_t *__restrict__ rings, int N, int L, int logn, CrtConsts cc,
-                  const CrtLimb *__restrict__ limbs, const uint32_t *__restrict__ index_map,
-                  const NttTable *__restrict__ plain_tabs, const double *__restrict__ thr, int tb, int *__restrict__ noise_bits) {
+crt_decode_kernel(const typename ArithOf<M>::T *__restrict__ V, uint64_t *__restrict__ rings, int N, int L, int logn, CrtConstsT<M> cc,
+                  const CrtLimbT<M> *__restrict__ limbs, const uint32_t *__restrict__ index_map,
+                  const NttTableT<typename ArithOf<M>::T, M> *__restrict__ plain_tabs, const typename ArithOf<M>::T *__restrict__ thr, int tb,
+                  int *__restrict__ noise_bits) {
+  using T = typename ArithOf<M>::T;
+  constexpr bool FP = std::is_same<M, Mod>::value;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_bits;
-  double *s = reinterpret_cast<double *>(smem);
+  T *s = reinterpret_cast<T *>(smem);
   const int n = 1 << logn, K = cc.K;
   if (threadIdx.x == 0) s_bits = 0;
   __syncthreads();
   int my_bits = 0;
-  double Qk[RS_MAX_K];
+  T Qk[RS_MAX_K];
   for (int k = 0; k < K; k++) Qk[k] = cc.Qmod[k].p;
   const size_t el = blockIdx.x;
   const int limb = (int)(el % (size_t)L);
-  const CrtLimb cl = limbs[limb];
-  const NttTable tab = plain_tabs[limb];
-  const Mod tmod = cl.tmod;
-  const double *v = V + el * (size_t)K * n;
+  const CrtLimbT<M> cl = limbs[limb];
+  const NttTableT<T, M> tab = plain_tabs[limb];
+  const M tmod = cl.tmod;
+  const T *v = V + el * (size_t)K * n;
   for (int x = threadIdx.x; x < n; x += blockDim.x) {
-    double d[RS_MAX_K];
+    T d[RS_MAX_K];
     d[0] = v[x];
     for (int k = 1; k < K; k++) {  // value = d0 + Q0*(d1 + Q1*(d2 + ...))
-      const Mod mk = cc.Qmod[k];
-      double acc = 0.0;
-      for (int i = k - 1; i >= 0; i--) acc = reduce(mulmod(acc, cc.Qi_mod_Qk[i][k], mk) + reduce(d[i], mk), mk);
-      d[k] = canon(mulmod(reduce(v[(size_t)k * n + x] - acc, mk), cc.prod_inv[k], mk), mk);
+      const M mk = cc.Qmod[k];
+      T acc = T(0);
+      for (int i = k - 1; i >= 0; i--) acc = reduce(addm(mulmod(acc, cc.Qi_mod_Qk[i][k], mk), digit_residue(d[i], mk), mk), mk);
+      d[k] = canon(mulmod(reduce(subm(v[(size_t)k * n + x], acc, mk), mk), cc.prod_inv[k], mk), mk);
     }
     bool upper = false;  // value > floor(Q/2)?
     for (int k = K - 1; k >= 0; k--)
@@ -119,10 +137,10 @@ crt_decode_kernel(const double *__restrict__ V, uint64_t *__restrict__ rings, in
         upper = d[k] > cc.half[k];
         break;
       }
-    my_bits = max(my_bits, magnitude_bits<double>(d, upper, Qk, thr, tb, K));
-    double r = 0.0;
-    for (int k = K - 1; k >= 0; k--) r = reduce(mulmod(r, cl.Qk_mod_t[k], tmod) + reduce(d[k], tmod), tmod);
-    if (upper) r -= cl.Q_mod_t;
+    my_bits = max(my_bits, magnitude_bits<T>(d, upper, Qk, thr, tb, K));
+    T r = T(0);
+    for (int k = K - 1; k >= 0; k--) r = reduce(addm(mulmod(r, cl.Qk_mod_t[k], tmod), digit_residue(d[k], tmod), tmod), tmod);
+    if (upper) r = subm(r, cl.Q_mod_t, tmod);
     r = reduce(r, tmod);
     if (cl.scale) r = reduce(mulmod(r, cl.F, tmod), tmod);  // SEAL's correction_factor of a switched ciphertext
     s[pidx(x)] = r;
@@ -131,44 +149,48 @@ crt_decode_kernel(const double *__restrict__ V, uint64_t *__restrict__ rings, in
   __syncthreads();
   if (threadIdx.x == 0) noise_bits[el] = s_bits;  // significant bits of the infinity norm of this ciphertext's noise polynomial
   if (!rings) return;                              // rs_enc_noise_budget: the budget only
-  lds_ntt_fwd(s, logn, tab.d_tw, 1, tmod, tab.fwd_red_mask);  // BatchEncoder::decode
+  lds_ntt_fwd(s, logn, tab.d_tw, 1, tmod, FP ? tab.fwd_red_mask : 0u);  // BatchEncoder::decode
   uint64_t *dst = rings + el * (size_t)N;
-  for (int i = threadIdx.x; i < N; i += blockDim.x) dst[i] = to_u64(canon(s[pidx((int)index_map[i])], tmod));
+  for (int i = threadIdx.x; i < N; i += blockDim.x) dst[i] = to_res(canon(s[pidx((int)index_map[i])], tmod));
 }
 
 // ---- encode ----------------------------------------------------------------------------------
 // One workgroup per (element, limb, prime j): c1 = a, c0 = -(a*s + t*e) + NTT(lift(BatchEncode(ring limb))).
 // Stream layout of oracle/rs_oracle.c rso_encrypt_symmetric: draws 1..n are the ternary error,
 // draw n + j*n + x + 1 is a_j[x].  grid (count * L, K); PER = n / blockDim <= 16
+template <class M>
 __global__ void __launch_bounds__(1024)
 encode_kernel(const uint64_t *__restrict__ rings, const uint64_t *__restrict__ sk, uint64_t *__restrict__ enc, uint64_t seed0,
-              int N, int L, int K, int logn, const uint32_t *__restrict__ index_map, const NttTable *__restrict__ plain_tabs,
-              const NttTable *__restrict__ coeff_tabs, const uint64_t *__restrict__ qint, const uint64_t *__restrict__ Qint) {
+              int N, int L, int K, int logn, const uint32_t *__restrict__ index_map,
+              const NttTableT<typename ArithOf<M>::T, M> *__restrict__ plain_tabs,
+              const NttTableT<typename ArithOf<M>::T, M> *__restrict__ coeff_tabs) {
+  using T = typename ArithOf<M>::T;
+  constexpr bool FP = std::is_same<M, Mod>::value;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *s = reinterpret_cast<double *>(smem);
+  T *s = reinterpret_cast<T *>(smem);
   const int n = 1 << logn;
   const size_t el = blockIdx.x;
   const size_t elem = el / (size_t)L;
   const int limb = (int)(el % (size_t)L), j = blockIdx.y;
-  const NttTable pt = plain_tabs[limb], ct = coeff_tabs[j];
-  const Mod tmod = pt.mod, mod = ct.mod;
-  const uint64_t t = qint[limb], Q = Qint[j];
+  const NttTableT<T, M> pt = plain_tabs[limb], ct = coeff_tabs[j];
+  const M tmod = pt.mod, mod = ct.mod;
+  const uint64_t t = modulus_u64(tmod), Q = modulus_u64(mod);
   const uint64_t seed = (seed0 + elem) * 1315423911ull + (uint64_t)limb + 1;  // rso_enc_encode's per-limb stream
   // BatchEncoder::encode: slot scatter + inverse NTT mod t
-  for (int p = threadIdx.x; p < n; p += blockDim.x) s[pidx(p)] = 0.0;
+  for (int p = threadIdx.x; p < n; p += blockDim.x) s[pidx(p)] = T(0);
   __syncthreads();
   const uint64_t *src = rings + el * (size_t)N;
-  for (int x = threadIdx.x; x < N; x += blockDim.x) s[pidx((int)index_map[x])] = from_u64(src[x]);
+  for (int x = threadIdx.x; x < N; x += blockDim.x) s[pidx((int)index_map[x])] = from_res<T>(src[x]);
   __syncthreads();
-  lds_ntt_inv(s, logn, pt.d_itw, 1, tmod, pt.inv_red_mask);
+  lds_ntt_inv(s, logn, pt.d_itw, 1, tmod, FP ? pt.inv_red_mask : 0u);
   // centred lift to Z_{Q_j} (in place; every thread touches only its own positions)
   for (int p = threadIdx.x; p < n; p += blockDim.x) {
-    const double c = canon(mulmod(reduce(s[pidx(p)], tmod), pt.ninv, tmod), tmod);
-    s[pidx(p)] = reduce(center(c, tmod), mod);
+    const T c = canon(mulmod(reduce(s[pidx(p)], tmod), pt.ninv, tmod), tmod);
+    s[pidx(p)] = lift_residue(lift_centered(c, tmod), mod);
   }
   __syncthreads();
-  lds_ntt_fwd(s, logn, ct.d_tw, 1, mod, ct.fwd_red_mask);
-  double P[16];
+  lds_ntt_fwd(s, logn, ct.d_tw, 1, mod, FP ? ct.fwd_red_mask : 0u);
+  T P[16];
 #pragma unroll
   for (int k = 0; k < 16; k++) {
     const int p = threadIdx.x + k * blockDim.x;
@@ -176,10 +198,10 @@ encode_kernel(const uint64_t *__restrict__ rings, const uint64_t *__restrict__ s
   }
   __syncthreads();
   // ternary error, NTT form
-  for (int p = threadIdx.x; p < n; p += blockDim.x) s[pidx(p)] = (double)((int)(splitmix_at(seed, (uint64_t)p + 1) % 3) - 1);
+  for (int p = threadIdx.x; p < n; p += blockDim.x) s[pidx(p)] = ternary_res((int)(splitmix_at(seed, (uint64_t)p + 1) % 3) - 1, mod);
   __syncthreads();
-  lds_ntt_fwd(s, logn, ct.d_tw, 1, mod, ct.fwd_red_mask);
-  const double tq = reduce(from_u64(t % Q), mod);
+  lds_ntt_fwd(s, logn, ct.d_tw, 1, mod, FP ? ct.fwd_red_mask : 0u);
+  const T tq = reduce(from_res<T>(t % Q), mod);
   uint64_t *c0 = enc + (el * 2 * K + j) * (size_t)n, *c1 = c0 + (size_t)K * n;
   const uint64_t *sj = sk + (size_t)j * n;
 #pragma unroll
@@ -187,151 +209,10 @@ encode_kernel(const uint64_t *__restrict__ rings, const uint64_t *__restrict__ s
     const int p = threadIdx.x + k * blockDim.x;
     if (p < n) {
       const uint64_t a = splitmix_at(seed, (uint64_t)n + (uint64_t)j * n + (uint64_t)p + 1) % Q;
-      const double as = mulmod(from_u64(a), from_u64(sj[p]), mod);
-      const double te = mulmod(tq, reduce(s[pidx(p)], mod), mod);
+      const T as = mulmod_dd(from_res<T>(a), from_res<T>(sj[p]), mod);
+      const T te = mulmod_dd(tq, reduce(s[pidx(p)], mod), mod);
       c1[p] = a;
-      c0[p] = to_u64(canon(P[k] - as - te, mod));
-    }
-  }
-}
-
-// ---- the same three kernels on the integer (Montgomery) arithmetic of intmod.hpp: contexts with a modulus >= 2^50.
-// Values are canonical residues; table constants are in Montgomery form (mulmod = data x constant, mulmod_dd = data x data).
-__global__ void __launch_bounds__(1024)
-decrypt_dot_kernel_int(const uint64_t *__restrict__ enc, const uint64_t *__restrict__ sk, uint64_t *__restrict__ V, int K, int logn,
-                       const NttTableI *__restrict__ coeff_tabs) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  uint64_t *s = reinterpret_cast<uint64_t *>(smem);
-  const int n = 1 << logn;
-  const size_t el = blockIdx.x;
-  const int j = blockIdx.y;
-  const NttTableI tab = coeff_tabs[j];
-  const ModI mod = tab.mod;
-  const uint64_t *c0 = enc + (el * 2 * K + j) * (size_t)n, *c1 = c0 + (size_t)K * n;
-  const uint64_t *sj = sk + (size_t)j * n;
-  for (int x = threadIdx.x; x < n; x += blockDim.x) s[pidx(x)] = addm(c0[x], mulmod_dd(c1[x], sj[x], mod), mod);
-  __syncthreads();
-  lds_ntt_inv(s, logn, tab.d_itw, 1, mod, 0u);
-  uint64_t *dst = V + (el * K + j) * (size_t)n;
-  for (int x = threadIdx.x; x < n; x += blockDim.x) dst[x] = mulmod(s[pidx(x)], tab.ninv, mod);
-}
-
-struct CrtConstsI {
-  int K;
-  ModI Qmod[RS_MAX_K];
-  uint64_t half[RS_MAX_K];                 // mixed-radix digits of floor(Q/2)
-  uint64_t prod_inv[RS_MAX_K];             // (prod_{i<k} Q_i)^-1 mod Q_k, Montgomery form
-  uint64_t Qi_mod_Qk[RS_MAX_K][RS_MAX_K];  // [i][k] = Q_i mod Q_k, Montgomery form
-};
-struct CrtLimbI {
-  ModI tmod;
-  uint64_t Qk_mod_t[RS_MAX_K];  // Montgomery form
-  uint64_t Q_mod_t;             // value
-  uint64_t F;                   // level factor, Montgomery form (CrtLimb)
-  int scale;
-};
-
-__global__ void __launch_bounds__(1024)
-crt_decode_kernel_int(const uint64_t *__restrict__ V, uint64_t *__restrict__ rings, int N, int L, int logn, CrtConstsI cc,
-                      const CrtLimbI *__restrict__ limbs, const uint32_t *__restrict__ index_map,
-                      const NttTableI *__restrict__ plain_tabs, const uint64_t *__restrict__ thr, int tb, int *__restrict__ noise_bits) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ int s_bits;
-  uint64_t *s = reinterpret_cast<uint64_t *>(smem);
-  const int n = 1 << logn, K = cc.K;
-  if (threadIdx.x == 0) s_bits = 0;
-  __syncthreads();
-  int my_bits = 0;
-  uint64_t Qk[RS_MAX_K];
-  for (int k = 0; k < K; k++) Qk[k] = cc.Qmod[k].p;
-  const size_t el = blockIdx.x;
-  const int limb = (int)(el % (size_t)L);
-  const CrtLimbI cl = limbs[limb];
-  const NttTableI tab = plain_tabs[limb];
-  const ModI tmod = cl.tmod;
-  const uint64_t *v = V + el * (size_t)K * n;
-  for (int x = threadIdx.x; x < n; x += blockDim.x) {
-    uint64_t d[RS_MAX_K];
-    d[0] = v[x];
-    for (int k = 1; k < K; k++) {  // value = d0 + Q0*(d1 + Q1*(d2 + ...))
-      const ModI mk = cc.Qmod[k];
-      uint64_t acc = 0;
-      for (int i = k - 1; i >= 0; i--) acc = addm(mulmod(acc, cc.Qi_mod_Qk[i][k], mk), d[i] % mk.p, mk);
-      d[k] = mulmod(subm(v[(size_t)k * n + x], acc, mk), cc.prod_inv[k], mk);
-    }
-    bool upper = false;  // value > floor(Q/2)?
-    for (int k = K - 1; k >= 0; k--)
-      if (d[k] != cc.half[k]) {
-        upper = d[k] > cc.half[k];
-        break;
-      }
-    my_bits = max(my_bits, magnitude_bits<uint64_t>(d, upper, Qk, thr, tb, K));
-    uint64_t r = 0;
-    for (int k = K - 1; k >= 0; k--) r = addm(mulmod(r, cl.Qk_mod_t[k], tmod), d[k] % tmod.p, tmod);
-    if (upper) r = subm(r, cl.Q_mod_t, tmod);
-    if (cl.scale) r = mulmod(r, cl.F, tmod);
-    s[pidx(x)] = r;
-  }
-  atomicMax(&s_bits, my_bits);
-  __syncthreads();
-  if (threadIdx.x == 0) noise_bits[el] = s_bits;
-  if (!rings) return;
-  lds_ntt_fwd(s, logn, tab.d_tw, 1, tmod, 0u);  // BatchEncoder::decode
-  uint64_t *dst = rings + el * (size_t)N;
-  for (int i = threadIdx.x; i < N; i += blockDim.x) dst[i] = s[pidx((int)index_map[i])];
-}
-
-__global__ void __launch_bounds__(1024)
-encode_kernel_int(const uint64_t *__restrict__ rings, const uint64_t *__restrict__ sk, uint64_t *__restrict__ enc, uint64_t seed0,
-                  int N, int L, int K, int logn, const uint32_t *__restrict__ index_map, const NttTableI *__restrict__ plain_tabs,
-                  const NttTableI *__restrict__ coeff_tabs) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  uint64_t *s = reinterpret_cast<uint64_t *>(smem);
-  const int n = 1 << logn;
-  const size_t el = blockIdx.x;
-  const size_t elem = el / (size_t)L;
-  const int limb = (int)(el % (size_t)L), j = blockIdx.y;
-  const NttTableI pt = plain_tabs[limb], ct = coeff_tabs[j];
-  const ModI tmod = pt.mod, mod = ct.mod;
-  const uint64_t t = tmod.p, Q = mod.p;
-  const uint64_t seed = (seed0 + elem) * 1315423911ull + (uint64_t)limb + 1;
-  for (int p = threadIdx.x; p < n; p += blockDim.x) s[pidx(p)] = 0;
-  __syncthreads();
-  const uint64_t *src = rings + el * (size_t)N;
-  for (int x = threadIdx.x; x < N; x += blockDim.x) s[pidx((int)index_map[x])] = src[x];
-  __syncthreads();
-  lds_ntt_inv(s, logn, pt.d_itw, 1, tmod, 0u);
-  for (int p = threadIdx.x; p < n; p += blockDim.x) {
-    const uint64_t c = mulmod(s[pidx(p)], pt.ninv, tmod);
-    s[pidx(p)] = lift_residue(lift_centered(c, tmod), mod);
-  }
-  __syncthreads();
-  lds_ntt_fwd(s, logn, ct.d_tw, 1, mod, 0u);
-  uint64_t P[16];
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    const int p = threadIdx.x + k * blockDim.x;
-    if (p < n) P[k] = s[pidx(p)];
-  }
-  __syncthreads();
-  for (int p = threadIdx.x; p < n; p += blockDim.x) {
-    const int e = (int)(splitmix_at(seed, (uint64_t)p + 1) % 3) - 1;
-    s[pidx(p)] = e < 0 ? Q - 1 : (uint64_t)e;
-  }
-  __syncthreads();
-  lds_ntt_fwd(s, logn, ct.d_tw, 1, mod, 0u);
-  const uint64_t tq = t % Q;
-  uint64_t *c0 = enc + (el * 2 * K + j) * (size_t)n, *c1 = c0 + (size_t)K * n;
-  const uint64_t *sj = sk + (size_t)j * n;
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    const int p = threadIdx.x + k * blockDim.x;
-    if (p < n) {
-      const uint64_t a = splitmix_at(seed, (uint64_t)n + (uint64_t)j * n + (uint64_t)p + 1) % Q;
-      const uint64_t as = mulmod_dd(a, sj[p], mod);
-      const uint64_t te = mulmod_dd(tq, s[pidx(p)], mod);
-      c1[p] = a;
-      c0[p] = subm(subm(P[k], as, mod), te, mod);
+      c0[p] = to_res(canon(subm(subm(P[k], as, mod), te, mod), mod));
     }
   }
 }
@@ -428,167 +309,117 @@ static int noise_verdict(rs_ctx *ctx, const int *d_bits, size_t count, int tb, b
   return RS_OK;
 }
 
-int rs::decode_impl(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
-                    rs_stream stream) {
-  if (count == 0) return RS_OK;
-  WsScope ws_scope(ctx, S(stream));  // holds ctx->mu: the lazily built constants below are built once
-  // Constants of the (context, level) that only decoding reads are built at the first call and kept on the device: the digits of
-  // 2^b - 1 here, the per-limb CRT constants below.  With the table arrays of the context itself, a warm decode makes no
-  // hipMalloc / hipFree and no pageable upload (each an implicit device-wide synchronisation; round-5 advice).
-  if (!ctx->d_noise_thr[K]) {
-    std::vector<uint64_t> thr_h;
-    ctx->noise_tb[K] = noise_thresholds(ctx, K, thr_h);
-    if (!ctx->use_int)
-      for (auto &x : thr_h) {  // digits < Q_k < 2^50: exact doubles
-        const double d = (double)x;
-        memcpy(&x, &d, 8);
-      }
-    void *p = nullptr;
-    RS_HIP(hipMalloc(&p, thr_h.size() * 8));
-    if (hipMemcpy(p, thr_h.data(), thr_h.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(p);
-      throw rs::Error(RS_ERR_HIP, "upload of the noise-threshold table failed");
-    }
-    ctx->d_noise_thr[K] = p;
+// a table of constants that stays on the device for the life of the context
+static void *upload_constants(const void *h, size_t bytes, const char *what) {
+  void *p = nullptr;
+  RS_HIP(hipMalloc(&p, bytes));
+  if (hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(p);
+    throw rs::Error(RS_ERR_HIP, std::string("upload of the ") + what + " failed");
   }
-  const int tb = ctx->noise_tb[K];
-  void *d_thr = ctx->d_noise_thr[K];
-  int *d_bits = (int *)ws_get(ctx, WS_NOISE_BITS, sizeof(int) * count * (size_t)ctx->L);
-  const int L = ctx->L, n = ctx->N_enc;
-  hipStream_t st = S(stream);
-  if (ctx->use_int) {  // the same composition on the integer arithmetic
-    using namespace host;
-    CrtConstsI cc;
-    memset(&cc, 0, sizeof(cc));
-    cc.K = K;
-    {
-      uint64_t carry = 0;
-      for (int k = K - 1; k >= 0; k--) {
-        const unsigned __int128 cur = (unsigned __int128)(ctx->Q[k] - 1) + (unsigned __int128)carry * ctx->Q[k];
-        cc.half[k] = (uint64_t)(cur >> 1);
-        carry = (uint64_t)(cur & 1);
-      }
-    }
-    for (int k = 0; k < K; k++) {
-      const uint64_t Qk = ctx->Q[k];
-      cc.Qmod[k] = HostArith<ModI>::make(Qk);
-      uint64_t prod = 1 % Qk;
-      for (int i = 0; i < k; i++) prod = host::mulmod(prod, ctx->Q[i] % Qk, Qk);
-      cc.prod_inv[k] = HostArith<ModI>::konst(k ? invmod(prod, Qk) : 1, Qk);
-      for (int i = 0; i < K; i++) cc.Qi_mod_Qk[i][k] = HostArith<ModI>::konst(ctx->Q[i] % Qk, Qk);
-    }
-    std::vector<CrtLimbI> hl(L);
-    for (int i = 0; i < L; i++) {
-      const uint64_t t = ctx->q[i];
-      memset(&hl[i], 0, sizeof(CrtLimbI));
-      hl[i].tmod = HostArith<ModI>::make(t);
-      uint64_t Qm = 1 % t;
-      for (int k = 0; k < K; k++) {
-        hl[i].Qk_mod_t[k] = HostArith<ModI>::konst(ctx->Q[k] % t, t);
-        Qm = host::mulmod(Qm, ctx->Q[k] % t, t);
-      }
-      hl[i].Q_mod_t = Qm;
-      uint64_t F = 1 % t;
-      for (int k = K; k < ctx->K; k++) F = host::mulmod(F, ctx->Q[k] % t, t);
-      hl[i].F = HostArith<ModI>::konst(F, t);
-      hl[i].scale = K < ctx->K;
-    }
-    if (!ctx->d_crt_limbs[K]) {
-      void *p = nullptr;
-      RS_HIP(hipMalloc(&p, sizeof(CrtLimbI) * L));
-      if (hipMemcpy(p, hl.data(), sizeof(CrtLimbI) * L, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(p);
-        throw rs::Error(RS_ERR_HIP, "upload of the CRT constants failed");
-      }
-      ctx->d_crt_limbs[K] = p;
-    }
-    const CrtLimbI *d_limbs = static_cast<const CrtLimbI *>(ctx->d_crt_limbs[K]);
-    uint64_t *V = (uint64_t *)ws_get(ctx, WS_STAGE_ROWS, count * (size_t)L * K * n * sizeof(uint64_t));
-    const size_t lds = padded_len((size_t)n) * sizeof(uint64_t);
-    const int thr = enc_threads(ctx->logN_enc);
-    set_max_dyn_lds((const void *)decrypt_dot_kernel_int, (int)lds);
-    set_max_dyn_lds((const void *)crt_decode_kernel_int, (int)lds);
-    const double cts = (double)count * L, words = cts * K * n;  // ciphertexts; words of c0 (= of c1, = of V)
-    {
-      ProfScope p(ctx, st, "decrypt_dot_kernel_int", words * 8 * 3 + (double)K * n * 8, 0.0);
-      hipLaunchKernelGGL(decrypt_dot_kernel_int, dim3((unsigned)(count * L), K), dim3(thr), lds, st, d_enc, d_sk, V, K, ctx->logN_enc,
-                         ctx->d_coeff_tabs_i);
-    }
-    {
-      ProfScope p(ctx, st, "crt_decode_kernel_int", words * 8 + (d_rings ? cts * ctx->N * 8 : 0.0) + cts * 4, 0.0);
-      hipLaunchKernelGGL(crt_decode_kernel_int, dim3((unsigned)(count * L)), dim3(thr), lds, st, V, d_rings, ctx->N, L, ctx->logN_enc,
-                         cc, d_limbs, ctx->d_index_map, ctx->d_plain_tabs_i, (const uint64_t *)d_thr, tb, d_bits);
-    }
-    RS_HIP(hipGetLastError());
-    RS_HIP(hipStreamSynchronize(st));
-    return noise_verdict(ctx, d_bits, count, tb, d_rings != nullptr, h_budget);
-  }
-  // host constants of the CRT composition
-  CrtConsts cc;
+  return p;
+}
+
+// host constants of the CRT composition at level K
+template <class M>
+static CrtConstsT<M> crt_consts(const rs_ctx *ctx, int K) {
+  using H = HostArith<M>;
+  CrtConstsT<M> cc;
   memset(&cc, 0, sizeof(cc));
   cc.K = K;
-  using namespace host;
-  {
-    uint64_t carry = 0;
-    for (int k = K - 1; k >= 0; k--) {  // digits of Q-1 are (Q_k - 1); halve from the top
-      const unsigned __int128 cur = (unsigned __int128)(ctx->Q[k] - 1) + (unsigned __int128)carry * ctx->Q[k];
-      cc.half[k] = (double)(uint64_t)(cur >> 1);
-      carry = (uint64_t)(cur & 1);
-    }
+  uint64_t carry = 0;
+  for (int k = K - 1; k >= 0; k--) {  // digits of Q-1 are (Q_k - 1); halve from the top
+    const unsigned __int128 cur = (unsigned __int128)(ctx->Q[k] - 1) + (unsigned __int128)carry * ctx->Q[k];
+    cc.half[k] = H::plain((uint64_t)(cur >> 1), ctx->Q[k]);
+    carry = (uint64_t)(cur & 1);
   }
   for (int k = 0; k < K; k++) {
     const uint64_t Qk = ctx->Q[k];
-    cc.Qmod[k] = Mod{(double)Qk, 1.0 / (double)Qk};
+    cc.Qmod[k] = H::make(Qk);
     uint64_t prod = 1 % Qk;
     for (int i = 0; i < k; i++) prod = host::mulmod(prod, ctx->Q[i] % Qk, Qk);
-    cc.prod_inv[k] = k ? balanced(invmod(prod, Qk), Qk) : 1.0;
-    for (int i = 0; i < K; i++) cc.Qi_mod_Qk[i][k] = balanced(ctx->Q[i] % Qk, Qk);
+    cc.prod_inv[k] = H::konst(k ? host::invmod(prod, Qk) : 1, Qk);
+    for (int i = 0; i < K; i++) cc.Qi_mod_Qk[i][k] = H::konst(ctx->Q[i] % Qk, Qk);
   }
-  std::vector<CrtLimb> hl(L);
-  for (int i = 0; i < L; i++) {
+  return cc;
+}
+
+// ... and its per-limb constants (uploaded once per level: decode_arith)
+template <class M>
+static std::vector<CrtLimbT<M>> crt_limbs(const rs_ctx *ctx, int K) {
+  using H = HostArith<M>;
+  std::vector<CrtLimbT<M>> hl(ctx->L);  // value-initialised: zero, padding included
+  for (int i = 0; i < ctx->L; i++) {
     const uint64_t t = ctx->q[i];
-    hl[i].tmod = Mod{(double)t, 1.0 / (double)t};
-    uint64_t Qm = 1 % t;
+    hl[i].tmod = H::make(t);
+    uint64_t Qm = 1 % t, F = 1 % t;
     for (int k = 0; k < K; k++) {
-      hl[i].Qk_mod_t[k] = balanced(ctx->Q[k] % t, t);
+      hl[i].Qk_mod_t[k] = H::konst(ctx->Q[k] % t, t);
       Qm = host::mulmod(Qm, ctx->Q[k] % t, t);
     }
-    hl[i].Q_mod_t = balanced(Qm, t);
-    uint64_t F = 1 % t;
     for (int k = K; k < ctx->K; k++) F = host::mulmod(F, ctx->Q[k] % t, t);
-    hl[i].F = balanced(F, t);
+    hl[i].Q_mod_t = H::plain(Qm, t);
+    hl[i].F = H::konst(F, t);
     hl[i].scale = K < ctx->K;
   }
-  if (!ctx->d_crt_limbs[K]) {
-    void *p = nullptr;
-    RS_HIP(hipMalloc(&p, sizeof(CrtLimb) * L));
-    if (hipMemcpy(p, hl.data(), sizeof(CrtLimb) * L, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(p);
-      throw rs::Error(RS_ERR_HIP, "upload of the CRT constants failed");
-    }
-    ctx->d_crt_limbs[K] = p;
+  return hl;
+}
+
+// decode_impl in the arithmetic M; the caller holds the context's WsScope
+template <class M>
+static int decode_arith(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
+                        hipStream_t st) {
+  using T = typename ArithOf<M>::T;
+  constexpr bool FP = std::is_same<M, Mod>::value;
+  const int L = ctx->L, n = ctx->N_enc, logn = ctx->logN_enc;
+  // Constants of the (context, level) that only decoding reads are built at the first call and kept on the device: the digits of
+  // 2^b - 1 and the per-limb CRT constants.  With the table arrays of the context itself, a warm decode makes no
+  // hipMalloc / hipFree and no pageable upload (each an implicit device-wide synchronisation; round-5 advice).
+  if (!ctx->d_noise_thr[K]) {
+    std::vector<uint64_t> digits;
+    ctx->noise_tb[K] = noise_thresholds(ctx, K, digits);
+    const std::vector<T> thr_h(digits.begin(), digits.end());  // plain values; digits < Q_k, and < 2^50 where T is double: exact
+    ctx->d_noise_thr[K] = upload_constants(thr_h.data(), thr_h.size() * sizeof(T), "noise-threshold table");
   }
-  const CrtLimb *d_limbs = static_cast<const CrtLimb *>(ctx->d_crt_limbs[K]);
-  double *V = (double *)ws_get(ctx, WS_STAGE_ROWS, count * (size_t)L * K * n * sizeof(double));
-  const size_t lds = padded_len((size_t)n) * sizeof(double);
-  const int thr = enc_threads(ctx->logN_enc);
-  set_max_dyn_lds((const void *)decrypt_dot_kernel, (int)lds);
-  set_max_dyn_lds((const void *)crt_decode_kernel, (int)lds);
+  if (!ctx->d_crt_limbs[K]) {
+    const std::vector<CrtLimbT<M>> hl = crt_limbs<M>(ctx, K);
+    ctx->d_crt_limbs[K] = upload_constants(hl.data(), hl.size() * sizeof(CrtLimbT<M>), "CRT constants");
+  }
+  const int tb = ctx->noise_tb[K];
+  const T *d_thr = static_cast<const T *>(ctx->d_noise_thr[K]);
+  const CrtLimbT<M> *d_limbs = static_cast<const CrtLimbT<M> *>(ctx->d_crt_limbs[K]);
+  const CrtConstsT<M> cc = crt_consts<M>(ctx, K);
+  int *d_bits = (int *)ws_get(ctx, WS_NOISE_BITS, sizeof(int) * count * (size_t)L);
+  T *V = (T *)ws_get(ctx, WS_STAGE_ROWS, count * (size_t)L * K * n * sizeof(T));
+  const size_t lds = padded_len((size_t)n) * sizeof(T);
+  const int thr = enc_threads(logn);
+  set_max_dyn_lds((const void *)decrypt_dot_kernel<M>, (int)lds);
+  set_max_dyn_lds((const void *)crt_decode_kernel<M>, (int)lds);
   const double cts = (double)count * L, words = cts * K * n;  // ciphertexts; words of c0 (= of c1, = of V)
   {
-    ProfScope p(ctx, st, "decrypt_dot_kernel", words * 8 * 3 + (double)K * n * 8, words * (7.0 + 7.0) + cts * K * ntt_fp64(n, ctx->logN_enc));
-    hipLaunchKernelGGL(decrypt_dot_kernel, dim3((unsigned)(count * L), K), dim3(thr), lds, st, d_enc, d_sk, V, K, ctx->logN_enc,
-                       ctx->d_coeff_tabs);
+    ProfScope p(ctx, st, CtxArith<M>::decrypt_dot_name, words * 8 * 3 + (double)K * n * 8,
+                FP ? words * (7.0 + 7.0) + cts * K * ntt_fp64(n, logn) : 0.0);
+    hipLaunchKernelGGL((decrypt_dot_kernel<M>), dim3((unsigned)(count * L), K), dim3(thr), lds, st, d_enc, d_sk, V, K, logn,
+                       CtxArith<M>::d_coeff(ctx));
   }
   {
-    ProfScope p(ctx, st, "crt_decode_kernel", words * 8 + (d_rings ? cts * ctx->N * 8 : 0.0) + cts * 4,
-                cts * n * 7.0 * (K * (K - 1) / 2.0 + 2.0 * K) + (d_rings ? cts * ntt_fp64(n, ctx->logN_enc) : 0.0));
-    hipLaunchKernelGGL(crt_decode_kernel, dim3((unsigned)(count * L)), dim3(thr), lds, st, V, d_rings, ctx->N, L, ctx->logN_enc,
-                       cc, d_limbs, ctx->d_index_map, ctx->d_plain_tabs, (const double *)d_thr, tb, d_bits);
+    ProfScope p(ctx, st, CtxArith<M>::crt_decode_name, words * 8 + (d_rings ? cts * ctx->N * 8 : 0.0) + cts * 4,
+                FP ? cts * n * 7.0 * (K * (K - 1) / 2.0 + 2.0 * K) + (d_rings ? cts * ntt_fp64(n, logn) : 0.0) : 0.0);
+    hipLaunchKernelGGL((crt_decode_kernel<M>), dim3((unsigned)(count * L)), dim3(thr), lds, st, V, d_rings, ctx->N, L, logn, cc, d_limbs,
+                       ctx->d_index_map, CtxArith<M>::d_plain(ctx), d_thr, tb, d_bits);
   }
   RS_HIP(hipGetLastError());
   RS_HIP(hipStreamSynchronize(st));
   return noise_verdict(ctx, d_bits, count, tb, d_rings != nullptr, h_budget);
+}
+
+int rs::decode_impl(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
+                    rs_stream stream) {
+  if (count == 0) return RS_OK;
+  WsScope ws_scope(ctx, S(stream));  // holds ctx->mu: the lazily built constants are built once
+  int rc = RS_OK;
+  dispatch_arith(ctx, [&](auto tag) { rc = decode_arith<decltype(tag)>(ctx, K, d_sk, d_enc, count, d_rings, h_budget, S(stream)); });
+  return rc;
 }
 
 extern "C" {
@@ -601,21 +432,14 @@ int rs_enc_encode(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_rings, si
   RS_REQUIRE(ctx->N_enc <= 16 * 1024, "encoding degree out of range");
   WsScope ws_scope(ctx, S(stream));
   hipStream_t st = S(stream);
-  if (ctx->use_int) {
-    const size_t lds = padded_len((size_t)ctx->N_enc) * sizeof(uint64_t);
-    const int thr = std::max(enc_threads(ctx->logN_enc), ctx->N_enc / 16);
-    set_max_dyn_lds((const void *)encode_kernel_int, (int)lds);
-    hipLaunchKernelGGL(encode_kernel_int, dim3((unsigned)(count * ctx->L), ctx->K), dim3(thr), lds, st, d_rings, d_sk, d_enc, seed,
-                       ctx->N, ctx->L, ctx->K, ctx->logN_enc, ctx->d_index_map, ctx->d_plain_tabs_i, ctx->d_coeff_tabs_i);
-    RS_HIP(hipGetLastError());
-    RS_HIP(hipStreamSynchronize(st));
-    return RS_OK;
-  }
-  const size_t lds = padded_len((size_t)ctx->N_enc) * sizeof(double);
   const int thr = std::max(enc_threads(ctx->logN_enc), ctx->N_enc / 16);
-  set_max_dyn_lds((const void *)encode_kernel, (int)lds);
-  hipLaunchKernelGGL(encode_kernel, dim3((unsigned)(count * ctx->L), ctx->K), dim3(thr), lds, st, d_rings, d_sk, d_enc, seed,
-                     ctx->N, ctx->L, ctx->K, ctx->logN_enc, ctx->d_index_map, ctx->d_plain_tabs, ctx->d_coeff_tabs, ctx->d_qint, ctx->d_Qint);
+  dispatch_arith(ctx, [&](auto tag) {
+    using M = decltype(tag);
+    const size_t lds = padded_len((size_t)ctx->N_enc) * sizeof(typename ArithOf<M>::T);
+    set_max_dyn_lds((const void *)encode_kernel<M>, (int)lds);
+    hipLaunchKernelGGL((encode_kernel<M>), dim3((unsigned)(count * ctx->L), ctx->K), dim3(thr), lds, st, d_rings, d_sk, d_enc, seed, ctx->N,
+                       ctx->L, ctx->K, ctx->logN_enc, ctx->d_index_map, CtxArith<M>::d_plain(ctx), CtxArith<M>::d_coeff(ctx));
+  });
   RS_HIP(hipGetLastError());
   RS_HIP(hipStreamSynchronize(st));
   RS_API_END
@@ -773,63 +597,34 @@ namespace rs {
 // reference's product loop (evaluation_domain.tcc:28-39).  hit[0] / hit[1] = min / max over slots of
 // the domain index the slot equals (0xFFFFFFFF: none): s IS a domain element -- the only case the
 // reference rejects (evaluation_domain.tcc:24-26) -- iff hit[0] == hit[1] != 0xFFFFFFFF.
+template <class M>
 __global__ void __launch_bounds__(256)
 lagrange_kernel(const uint64_t *__restrict__ s, uint64_t *__restrict__ Ht, uint64_t *__restrict__ U, uint64_t *__restrict__ Zt,
-                const double *__restrict__ c /* [L][m] */, unsigned *__restrict__ hit, size_t m, int N, int L,
-                const Mod *__restrict__ qmod) {
+                const typename ArithOf<M>::T *__restrict__ c /* [L][m], table constants */, unsigned *__restrict__ hit, size_t m, int N, int L,
+                const M *__restrict__ qmod) {
+  using T = typename ArithOf<M>::T;
   const size_t S = (size_t)L * N, i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= S) return;
   const int limb = (int)(i / (size_t)N);
-  const Mod mod = qmod[limb];
-  const double sv = center(from_u64(s[i]), mod);
+  const M mod = qmod[limb];
+  const T sv = center(from_res<T>(s[i]), mod);
   unsigned my_hit = 0xFFFFFFFFu;
-  double suf = 1.0;
+  T suf = T(1);
   for (size_t j = m; j-- > 0;) {
-    U[j * S + i] = to_u64(canon(suf, mod));
-    const double d = reduce(sv - (double)j, mod);
-    if (canon(d, mod) == 0.0) my_hit = (unsigned)j;
-    suf = mulmod(suf, d, mod);
-  }
-  Zt[i] = to_u64(canon(suf, mod));
-  double pre = 1.0, pw = 1.0;
-  for (size_t j = 0; j <= m; j++) {
-    Ht[j * S + i] = to_u64(canon(pw, mod));
-    pw = mulmod(pw, sv, mod);
-    if (j < m) {
-      const double v = mulmod(pre, center(from_u64(U[j * S + i]), mod), mod);
-      U[j * S + i] = to_u64(canon(mulmod(v, c[(size_t)limb * m + j], mod), mod));
-      pre = mulmod(pre, reduce(sv - (double)j, mod), mod);
-    }
-  }
-  atomicMin(&hit[0], my_hit);
-  atomicMax(&hit[1], my_hit);
-}
-__global__ void __launch_bounds__(256)
-lagrange_kernel_int(const uint64_t *__restrict__ s, uint64_t *__restrict__ Ht, uint64_t *__restrict__ U, uint64_t *__restrict__ Zt,
-                    const uint64_t *__restrict__ c /* [L][m], Montgomery form */, unsigned *__restrict__ hit, size_t m, int N, int L,
-                    const ModI *__restrict__ qmod) {
-  const size_t S = (size_t)L * N, i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= S) return;
-  const int limb = (int)(i / (size_t)N);
-  const ModI mod = qmod[limb];
-  const uint64_t sv = s[i];
-  unsigned my_hit = 0xFFFFFFFFu;
-  uint64_t suf = 1;
-  for (size_t j = m; j-- > 0;) {
-    U[j * S + i] = suf;
-    const uint64_t d = subm(sv, small_val((uint64_t)j, mod), mod);
-    if (d == 0) my_hit = (unsigned)j;
+    U[j * S + i] = to_res(canon(suf, mod));
+    const T d = reduce(subm(sv, small_val((uint64_t)j, mod), mod), mod);
+    if (canon(d, mod) == T(0)) my_hit = (unsigned)j;
     suf = mulmod_dd(suf, d, mod);
   }
-  Zt[i] = suf;
-  uint64_t pre = 1, pw = 1;
+  Zt[i] = to_res(canon(suf, mod));
+  T pre = T(1), pw = T(1);
   for (size_t j = 0; j <= m; j++) {
-    Ht[j * S + i] = pw;
+    Ht[j * S + i] = to_res(canon(pw, mod));
     pw = mulmod_dd(pw, sv, mod);
     if (j < m) {
-      const uint64_t v = mulmod_dd(pre, U[j * S + i], mod);
-      U[j * S + i] = mulmod(v, c[(size_t)limb * m + j], mod);
-      pre = mulmod_dd(pre, subm(sv, small_val((uint64_t)j, mod), mod), mod);
+      const T v = mulmod_dd(pre, center(from_res<T>(U[j * S + i]), mod), mod);
+      U[j * S + i] = to_res(canon(mulmod(v, c[(size_t)limb * m + j], mod), mod));
+      pre = mulmod_dd(pre, reduce(subm(sv, small_val((uint64_t)j, mod), mod), mod), mod);
     }
   }
   atomicMin(&hit[0], my_hit);
@@ -863,24 +658,23 @@ void instance_map_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uint6
   guard.p.push_back(D);
   guard.st = st;
   if (wipe) guard.wipe_p = D, guard.wipe_bytes = m * SW * sizeof(uint64_t);
-  std::vector<uint64_t> hc;  // slot-constant factors c_j [L][m], table constants of the context's arithmetic
-  RS_DISPATCH_ARITH(ctx, lagrange_constants<Mod>(ctx, m, hc), lagrange_constants<ModI>(ctx, m, hc));
-  double *d_c = nullptr;
-  RS_HIP(hipMalloc(&d_c, hc.size() * sizeof(double)));
+  std::vector<uint64_t> hc;  // slot-constant factors c_j [L][m], table constants of the context's arithmetic as 64-bit words
+  dispatch_arith(ctx, [&](auto tag) { lagrange_constants<decltype(tag)>(ctx, m, hc); });
+  uint64_t *d_c = nullptr;
+  RS_HIP(hipMalloc(&d_c, hc.size() * sizeof(uint64_t)));
   guard.p.push_back(d_c);
   unsigned *d_hit = nullptr;
   RS_HIP(hipMalloc(&d_hit, 2 * sizeof(unsigned)));
   guard.p.push_back(d_hit);
   const unsigned hit0[2] = {0xFFFFFFFFu, 0u};
   unsigned hit[2];
-  RS_HIP(hipMemcpyAsync(d_c, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  RS_HIP(hipMemcpyAsync(d_c, hc.data(), hc.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   RS_HIP(hipMemcpyAsync(d_hit, hit0, sizeof(hit0), hipMemcpyHostToDevice, st));
-  if (ctx->use_int)
-    hipLaunchKernelGGL(lagrange_kernel_int, dim3((unsigned)((SW + 255) / 256)), dim3(256), 0, st, d_s, d_Ht, D, d_Zt,
-                       reinterpret_cast<const uint64_t *>(d_c), d_hit, m, ctx->N, L, ctx->d_qmod_i);
-  else
-    hipLaunchKernelGGL(lagrange_kernel, dim3((unsigned)((SW + 255) / 256)), dim3(256), 0, st, d_s, d_Ht, D, d_Zt, d_c, d_hit, m,
-                       ctx->N, L, ctx->d_qmod);
+  dispatch_arith(ctx, [&](auto tag) {
+    using M = decltype(tag);
+    hipLaunchKernelGGL((lagrange_kernel<M>), dim3((unsigned)((SW + 255) / 256)), dim3(256), 0, st, d_s, d_Ht, D, d_Zt,
+                       reinterpret_cast<const typename ArithOf<M>::T *>(d_c), d_hit, m, ctx->N, L, CtxArith<M>::qmod(ctx));
+  });
   RS_HIP(hipGetLastError());
   RS_HIP(hipMemcpyAsync(hit, d_hit, sizeof(hit), hipMemcpyDeviceToHost, st));
   RS_HIP(hipStreamSynchronize(st));  // hc, hit

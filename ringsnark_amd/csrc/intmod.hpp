@@ -14,7 +14,8 @@
 // and no value ever has to be converted into or out of Montgomery form.
 //
 // The kernels are written once against the overload set {mulmod, mulmod_dd, addm, subm, negm, reduce, canon,
-// center, from_res<T>, to_res} and instantiated for (double, Mod) and (uint64_t, ModI).
+// center, from_res<T>, to_res, and the conversions below: small_val, lift_*, digit_residue, ternary_res, modulus_u64}
+// and instantiated for (double, Mod) and (uint64_t, ModI).
 #pragma once
 #include <cstdint>
 
@@ -69,6 +70,12 @@ RS_HD uint64_t lift_residue(int64_t v, const ModI &Q) {
   const int64_t r = v % (int64_t)Q.p;
   return (uint64_t)(r < 0 ? r + (int64_t)Q.p : r);
 }
+// the residue modulo Q of a canonical value of ANOTHER modulus (a mixed-radix digit of the CRT composition), unsigned
+RS_HD uint64_t digit_residue(uint64_t d, const ModI &Q) { return d % Q.p; }
+// the residue of a ternary error e in {-1, 0, 1}
+RS_HD uint64_t ternary_res(int e, const ModI &Q) { return e < 0 ? Q.p - 1 : (uint64_t)e; }
+// the modulus as an integer
+RS_HD uint64_t modulus_u64(const ModI &m) { return m.p; }
 
 // ---- the same vocabulary for the FP64 arithmetic (f64mod.hpp) -------------------------------------------------
 RS_HD double mulmod_dd(double a, double b, const Mod &m) { return mulmod(a, b, m); }
@@ -81,6 +88,9 @@ RS_HD double small_val(uint64_t v, const Mod &) { return (double)v; }
 RS_HD double konst_value(double c, const Mod &) { return c; }
 RS_HD double lift_centered(double c, const Mod &t) { return center(c, t); }
 RS_HD double lift_residue(double v, const Mod &Q) { return reduce(v, Q); }
+RS_HD double digit_residue(double d, const Mod &Q) { return reduce(d, Q); }
+RS_HD double ternary_res(int e, const Mod &) { return (double)e; }
+RS_HD uint64_t modulus_u64(const Mod &m) { return (uint64_t)m.p; }
 
 template <class T>
 RS_HD T from_res(uint64_t v);

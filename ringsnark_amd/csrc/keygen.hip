@@ -35,8 +35,6 @@ __device__ __forceinline__ uint64_t lift_minus_te(uint64_t c, int e, const ModI 
   const uint64_t x = lift_residue(lift_centered(c, tmod), mod), tq = tmod.p % mod.p;
   return e > 0 ? subm(x, tq, mod) : (e < 0 ? addm(x, tq, mod) : x);
 }
-__device__ __forceinline__ uint64_t modulus_u64(const Mod &m) { return (uint64_t)m.p; }
-__device__ __forceinline__ uint64_t modulus_u64(const ModI &m) { return m.p; }
 
 // One workgroup per (element, limb); PER = n / blockDim <= 16.  Stream layout of oracle/rs_oracle.c rso_encrypt_symmetric,
 // as encode_kernel: draws 1..n are the ternary error (shared by the K primes), draw n + j*n + x + 1 is a_j[x].
@@ -136,12 +134,11 @@ static void encode_linear_launch(rs_ctx *ctx, const LinRows &lf, const uint64_t 
 // pub: the seed of the public stream (== seed: keygen.h); compact: the seeded layout, c0 only
 static void encode_linear(rs_ctx *ctx, const LinRows &lf, const uint64_t *d_sk, size_t count, uint64_t seed, uint64_t pub, bool compact,
                           uint64_t *d_enc, hipStream_t st) {
-  if (compact)
-    RS_DISPATCH_ARITH(ctx, (encode_linear_launch<Mod, true>(ctx, lf, d_sk, count, seed, pub, d_enc, st)),
-                      (encode_linear_launch<ModI, true>(ctx, lf, d_sk, count, seed, pub, d_enc, st)));
-  else
-    RS_DISPATCH_ARITH(ctx, (encode_linear_launch<Mod, false>(ctx, lf, d_sk, count, seed, pub, d_enc, st)),
-                      (encode_linear_launch<ModI, false>(ctx, lf, d_sk, count, seed, pub, d_enc, st)));
+  dispatch_arith(ctx, [&](auto tag) {
+    using M = decltype(tag);
+    if (compact) encode_linear_launch<M, true>(ctx, lf, d_sk, count, seed, pub, d_enc, st);
+    else encode_linear_launch<M, false>(ctx, lf, d_sk, count, seed, pub, d_enc, st);
+  });
 }
 
 constexpr size_t KEYGEN_HOST_TILE = 64;  // elements per staging buffer of a host-resident key when the caller names none

@@ -7,7 +7,7 @@
 //     u    = (-last * p^-1) mod t                 canonical in [0, t)
 //     c'_j = (c_j - NTT_{Q_j}((last + u p) mod Q_j)) * p^-1 mod Q_j        for every j < K_in - 1
 // last + u p = 0 mod p and = last mod t, so subtracting it makes the ciphertext divisible by p without moving the
-// plaintext; the division leaves m * p^-1 mod t, which the level decode undoes (encoding.hip, CrtLimb::F).
+// plaintext; the division leaves m * p^-1 mod t, which the level decode undoes (encoding.hip, CrtLimbT::F).
 // Every quantity is a residue: whichever representatives the arithmetic holds on the way, the words written are the
 // canonical ones, so the kernel's output is defined by the three lines above alone (ringsnark_amd/modswitch.py).
 //
@@ -122,7 +122,7 @@ static void mod_switch_run(rs_ctx *ctx, const uint64_t *d_in, size_t count, int 
   const uint64_t *src = d_in;
   for (int k = K_in, step = 0; k > K_out; k--, step++) {
     uint64_t *dst = k - 1 == K_out ? d_out : level[step & 1];
-    RS_DISPATCH_ARITH(ctx, (mod_switch_step<Mod>(ctx, src, dst, polys, k, st)), (mod_switch_step<ModI>(ctx, src, dst, polys, k, st)));
+    dispatch_arith(ctx, [&](auto tag) { mod_switch_step<decltype(tag)>(ctx, src, dst, polys, k, st); });
     src = dst;
   }
 }

@@ -716,8 +716,7 @@ static void msm_run_arith(rs_ctx *ctx, const MsmKey &key, const rs_msm_vec *vecs
 
 void msm_run(rs_ctx *ctx, const MsmKey &key, const rs_msm_vec *vecs, int n_vecs, int n_groups, uint64_t *d_out,
              const uint64_t *const *addends, size_t *h_used, hipStream_t st, const MsmLin *lin, bool wide_blocks) {
-  RS_DISPATCH_ARITH(ctx, (msm_run_arith<Mod>(ctx, key, vecs, n_vecs, n_groups, d_out, addends, h_used, st, lin, wide_blocks)),
-                    (msm_run_arith<ModI>(ctx, key, vecs, n_vecs, n_groups, d_out, addends, h_used, st, lin, wide_blocks)));
+  dispatch_arith(ctx, [&](auto tag) { msm_run_arith<decltype(tag)>(ctx, key, vecs, n_vecs, n_groups, d_out, addends, h_used, st, lin, wide_blocks); });
 }
 // can a call with linear-form vectors be served? (FP64 context on the wide plaintext kernel)
 bool msm_supports_lin(const rs_ctx *ctx) {
@@ -726,15 +725,12 @@ bool msm_supports_lin(const rs_ctx *ctx) {
 void batch_encode_run(rs_ctx *ctx, const uint64_t *d_rings, uint64_t *d_plain, size_t count, hipStream_t st) {
   if (!count) return;
   const size_t lds = padded_len((size_t)ctx->N_enc) * sizeof(double);
-  if (ctx->use_int) {
-    set_max_dyn_lds((const void *)batch_encode_kernel<ModI>, (int)lds);
-    hipLaunchKernelGGL(batch_encode_kernel<ModI>, dim3((unsigned)count, ctx->L), dim3(tile_threads(ctx->logN_enc)), lds, st, d_rings, d_plain,
-                       ctx->N, ctx->L, ctx->logN_enc, ctx->d_index_map, ctx->d_plain_tabs_i);
-  } else {
-    set_max_dyn_lds((const void *)batch_encode_kernel<Mod>, (int)lds);
-    hipLaunchKernelGGL(batch_encode_kernel<Mod>, dim3((unsigned)count, ctx->L), dim3(tile_threads(ctx->logN_enc)), lds, st, d_rings, d_plain,
-                       ctx->N, ctx->L, ctx->logN_enc, ctx->d_index_map, ctx->d_plain_tabs);
-  }
+  dispatch_arith(ctx, [&](auto tag) {
+    using M = decltype(tag);
+    set_max_dyn_lds((const void *)batch_encode_kernel<M>, (int)lds);
+    hipLaunchKernelGGL(batch_encode_kernel<M>, dim3((unsigned)count, ctx->L), dim3(tile_threads(ctx->logN_enc)), lds, st, d_rings, d_plain,
+                       ctx->N, ctx->L, ctx->logN_enc, ctx->d_index_map, CtxArith<M>::d_plain(ctx));
+  });
   RS_HIP(hipGetLastError());
 }
 

@@ -119,10 +119,10 @@ int rs_poly_multiply(rs_ctx *ctx, const uint64_t *d_a, size_t na, const uint64_t
   if (na && nb) {
     const size_t rows = written = na + nb - 1;
     const unsigned by = (unsigned)((S_ / 2 + 255) / 256);
-    if (ctx->use_int)
-      hipLaunchKernelGGL(poly_mul_kernel<ModI>, dim3((unsigned)rows, by), dim3(256), 0, st, d_a, na, d_b, nb, d_out, ctx->N, ctx->L, ctx->d_qmod_i);
-    else
-      hipLaunchKernelGGL(poly_mul_kernel<Mod>, dim3((unsigned)rows, by), dim3(256), 0, st, d_a, na, d_b, nb, d_out, ctx->N, ctx->L, ctx->d_qmod);
+    dispatch_arith(ctx, [&](auto tag) {
+      using M = decltype(tag);
+      hipLaunchKernelGGL(poly_mul_kernel<M>, dim3((unsigned)rows, by), dim3(256), 0, st, d_a, na, d_b, nb, d_out, ctx->N, ctx->L, CtxArith<M>::qmod(ctx));
+    });
     RS_HIP(hipGetLastError());
     len = normalised_len(ctx, d_out, rows, st);
   }
@@ -141,10 +141,10 @@ int rs_poly_add(rs_ctx *ctx, const uint64_t *d_a, size_t na, const uint64_t *d_b
   const size_t rows = std::max(na, nb), S_ = ctx->ring_words();
   if (rows) {
     const unsigned blocks = (unsigned)std::min<size_t>((rows * S_ + 255) / 256, 4096);
-    if (ctx->use_int)
-      hipLaunchKernelGGL(poly_add_kernel<ModI>, dim3(blocks), dim3(256), 0, st, d_a, na, d_b, nb, d_out, S_, ctx->N, ctx->L, ctx->d_qmod_i);
-    else
-      hipLaunchKernelGGL(poly_add_kernel<Mod>, dim3(blocks), dim3(256), 0, st, d_a, na, d_b, nb, d_out, S_, ctx->N, ctx->L, ctx->d_qmod);
+    dispatch_arith(ctx, [&](auto tag) {
+      using M = decltype(tag);
+      hipLaunchKernelGGL(poly_add_kernel<M>, dim3(blocks), dim3(256), 0, st, d_a, na, d_b, nb, d_out, S_, ctx->N, ctx->L, CtxArith<M>::qmod(ctx));
+    });
     RS_HIP(hipGetLastError());
   }
   if (h_len) *h_len = normalised_len(ctx, d_out, rows, st);
@@ -188,12 +188,11 @@ int rs_poly_divide(rs_ctx *ctx, const uint64_t *d_num, size_t nn, const uint64_t
     RS_HIP(hipMalloc(&rem, nn * S_ * sizeof(uint64_t)));
     guard.b = rem;
     RS_HIP(hipMemcpyAsync(rem, d_num, nn * S_ * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    if (ctx->use_int)
-      hipLaunchKernelGGL(poly_div_kernel<ModI>, dim3((unsigned)((S_ + 255) / 256)), dim3(256), 0, st, rem, nn, d_den, nd, lead_inv, d_quot,
-                         ctx->N, ctx->L, ctx->d_qmod_i);
-    else
-      hipLaunchKernelGGL(poly_div_kernel<Mod>, dim3((unsigned)((S_ + 255) / 256)), dim3(256), 0, st, rem, nn, d_den, nd, lead_inv, d_quot,
-                         ctx->N, ctx->L, ctx->d_qmod);
+    dispatch_arith(ctx, [&](auto tag) {
+      using M = decltype(tag);
+      hipLaunchKernelGGL(poly_div_kernel<M>, dim3((unsigned)((S_ + 255) / 256)), dim3(256), 0, st, rem, nn, d_den, nd, lead_inv, d_quot,
+                         ctx->N, ctx->L, CtxArith<M>::qmod(ctx));
+    });
     RS_HIP(hipGetLastError());
     WsScope ws_scope(ctx, st);
     len = normalised_len(ctx, d_quot, nn - nd + 1, st);  // synchronises: rem / lead_inv may be freed

@@ -416,12 +416,11 @@ int rs_chain_assignment(rs_ctx *ctx, uint64_t *d_assignment, size_t m, rs_stream
   RS_API_BEGIN_CTX(ctx)
   RS_REQUIRE(ctx && d_assignment, "null argument");
   const size_t S_ = ctx->ring_words();
-  if (ctx->use_int)
-    hipLaunchKernelGGL(chain_kernel<ModI>, dim3((unsigned)((S_ + 255) / 256)), dim3(256), 0, S(stream), d_assignment, m, ctx->N,
-                       ctx->L, ctx->d_qmod_i);
-  else
-    hipLaunchKernelGGL(chain_kernel<Mod>, dim3((unsigned)((S_ + 255) / 256)), dim3(256), 0, S(stream), d_assignment, m, ctx->N,
-                       ctx->L, ctx->d_qmod);
+  dispatch_arith(ctx, [&](auto tag) {
+    using M = decltype(tag);
+    hipLaunchKernelGGL(chain_kernel<M>, dim3((unsigned)((S_ + 255) / 256)), dim3(256), 0, S(stream), d_assignment, m, ctx->N, ctx->L,
+                       CtxArith<M>::qmod(ctx));
+  });
   RS_HIP(hipGetLastError());
   RS_API_END
 }

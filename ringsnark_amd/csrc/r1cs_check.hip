@@ -159,8 +159,7 @@ int rs_r1cs_check(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_assignment, 
     RS_HIP(hipMemsetAsync(rep, 0, sizeof(unsigned long long) * CHECK_WORDS, st));
     RS_HIP(hipMemsetAsync(rep, 0xFF, sizeof(unsigned long long), st));
     RS_HIP(hipMemsetAsync(flags, 0, m, st));
-    RS_DISPATCH_ARITH(ctx, (r1cs_check_run<Mod>(ctx, cs, d_assignment, flags, rep, st)),
-                      (r1cs_check_run<ModI>(ctx, cs, d_assignment, flags, rep, st)));
+    dispatch_arith(ctx, [&](auto tag) { r1cs_check_run<decltype(tag)>(ctx, cs, d_assignment, flags, rep, st); });
     unsigned long long h[CHECK_WORDS];
     RS_HIP(hipMemcpyAsync(h, rep, sizeof(h), hipMemcpyDeviceToHost, st));
     RS_HIP(hipStreamSynchronize(st));

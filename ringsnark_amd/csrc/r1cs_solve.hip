@@ -415,8 +415,7 @@ int rs_r1cs_solve(rs_ctx *ctx, const rs_r1cs_solve_plan *plan, uint64_t *d_assig
   if (!launches.empty()) {
     std::unique_lock<std::mutex> lk(ctx->mu, std::defer_lock);
     if (ctx->profiling) lk.lock();  // the record ProfScope appends to belongs to the holder of mu
-    RS_DISPATCH_ARITH(ctx, (solve_run<Mod>(ctx, plan, d_assignment, launches, S(stream))),
-                      (solve_run<ModI>(ctx, plan, d_assignment, launches, S(stream))));
+    dispatch_arith(ctx, [&](auto tag) { solve_run<decltype(tag)>(ctx, plan, d_assignment, launches, S(stream)); });
   }
   if (h_stats) *h_stats = stats;
   RS_API_END

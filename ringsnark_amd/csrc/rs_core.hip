@@ -579,8 +579,7 @@ static void launch_pointwise_arith(rs_ctx *ctx, uint64_t *dst, const uint64_t *a
 template <int OP>
 static void launch_pointwise(rs_ctx *ctx, uint64_t *dst, const uint64_t *a, const uint64_t *b, size_t count,
                              uint64_t scalar, hipStream_t st) {
-  RS_DISPATCH_ARITH(ctx, (launch_pointwise_arith<OP, Mod>(ctx, dst, a, b, count, scalar, st)),
-                    (launch_pointwise_arith<OP, ModI>(ctx, dst, a, b, count, scalar, st)));
+  dispatch_arith(ctx, [&](auto tag) { launch_pointwise_arith<OP, decltype(tag)>(ctx, dst, a, b, count, scalar, st); });
 }
 
 // slot-wise inverse by Fermat (a^(p-2)); flags[0] |= 1 if any slot is zero.

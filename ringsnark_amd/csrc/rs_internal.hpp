@@ -272,6 +272,8 @@ struct CtxArith<Mod> {
   static const Mod *Qmod(const rs_ctx *c) { return c->d_Qmod; }
   static const Table *d_plain(const rs_ctx *c) { return c->d_plain_tabs; }
   static const Table *d_coeff(const rs_ctx *c) { return c->d_coeff_tabs; }
+  // names of the decode kernels in a profile (ProfScope): committed profiles are joined by them
+  static constexpr const char *decrypt_dot_name = "decrypt_dot_kernel", *crt_decode_name = "crt_decode_kernel";
 };
 template <>
 struct CtxArith<ModI> {
@@ -283,22 +285,19 @@ struct CtxArith<ModI> {
   static const ModI *Qmod(const rs_ctx *c) { return c->d_Qmod_i; }
   static const Table *d_plain(const rs_ctx *c) { return c->d_plain_tabs_i; }
   static const Table *d_coeff(const rs_ctx *c) { return c->d_coeff_tabs_i; }
+  static constexpr const char *decrypt_dot_name = "decrypt_dot_kernel_int", *crt_decode_name = "crt_decode_kernel_int";
 };
-// run `f(Mod{})` or `f(ModI{})` according to the context's arithmetic
-#define RS_DISPATCH_ARITH(ctx, CALL_FP, CALL_INT) \
-  do {                                            \
-    if ((ctx)->use_int) {                         \
-      CALL_INT;                                   \
-    } else {                                      \
-      CALL_FP;                                    \
-    }                                             \
-  } while (0)
+// run `f(Mod{})` or `f(ModI{})` according to the context's arithmetic; f is a generic lambda that names its arithmetic
+// as `using M = decltype(tag)`, so the call it makes is written once
+template <class F>
+void dispatch_arith(const rs_ctx *ctx, F &&f) {
+  if (ctx->use_int) f(ModI{});
+  else f(Mod{});
+}
 // The context's workspace `slot`, grown to `bytes`.  A slot that grows is freed and allocated again, so a pointer taken
 // from a slot is dead after the next ws_get of the same slot within the same WsScope.
 void *ws_get(rs_ctx *ctx, WsSlot slot, size_t bytes);
-// Holds the context lock for one API call on `st` and, on exit, stamps every workspace buffer the
-// call touched with an event on `st` (see DeviceBuf).  Every entry point that calls ws_get owns one.
-// Also pins the HIP current device of the calling thread to the context's device for the call.
+// Pins the HIP current device of the calling thread to the context's device for the call.
 struct DeviceGuard {
   int prev = -1;
   explicit DeviceGuard(int dev) {
@@ -310,21 +309,18 @@ struct DeviceGuard {
     if (prev >= 0) (void)hipSetDevice(prev);
   }
 };
-// Times ONE kernel launch when profiling is on (no-op otherwise):  { ProfScope p(...); launch; }
-// A coefficient vector of an inner product given as a linear form instead of rows: vector[t] = sum_e lv_e[t] * r_{k_e}
-// (slot-wise), lv_e[t] = Lcols[(col_e * L + limb) * Mlen + t] slot-constant scalars and r_0 = 1, r_k = k-th ring element of
-// `rings` -- the io vectors of the witness map (witness.hip, "io vectors without interpolation").  The plaintext of such a
-// vector is the same linear form of the PLAINTEXTS of the r_k (the inverse transform is linear over Z_q), so the inner
-// product never materialises the rows nor transforms them: P = batch-encoded [1, r_1, ..] as [(nk)][L][N_enc] canonical words.
-struct MsmLin {
-  const int *k = nullptr, *col = nullptr;  // device arrays [count]
-  int count = 0;
-  const double *Lcols = nullptr;
-  size_t Mlen = 0;
-  const uint64_t *P = nullptr;
-  unsigned long long T = 0;  // terms
+// Holds the context lock for one API call on `st` and, on exit, stamps every workspace buffer the
+// call touched with an event on `st` (see DeviceBuf).  Every entry point that calls ws_get owns one.
+struct WsScope {
+  rs_ctx *ctx;
+  std::unique_lock<std::mutex> lk;
+  WsScope(rs_ctx *c, hipStream_t st) : ctx(c), lk(c->mu) {
+    ctx->cur_stream = st;
+    ctx->ws_touched = 0;
+  }
+  ~WsScope();
 };
-
+// Times ONE kernel launch when profiling is on (no-op otherwise):  { ProfScope p(...); launch; }
 struct ProfScope {
   rs_ctx *ctx;
   hipStream_t st;
@@ -335,15 +331,6 @@ struct ProfScope {
 // FP64 instruction counts used for the rooflines: a lazy butterfly is 8 instructions (6 mulmod +
 // add + sub), a pointwise modular multiply 7 (mulmod + a reduce/canon step), per lane.
 inline double ntt_fp64(double n, double logn) { return 8.0 * (n / 2.0) * logn; }
-struct WsScope {
-  rs_ctx *ctx;
-  std::unique_lock<std::mutex> lk;
-  WsScope(rs_ctx *c, hipStream_t st) : ctx(c), lk(c->mu) {
-    ctx->cur_stream = st;
-    ctx->ws_touched = 0;
-  }
-  ~WsScope();
-};
 template <class M>
 NttTableT<typename HostArith<M>::T, M> make_negacyclic_table(uint64_t p, int logn);
 template <class T, class M>
@@ -368,6 +355,19 @@ struct MsmKey {
   size_t window;                         // != 0: `window` elements are stored and element t lives at index t % window (tiled keys, ringsnark_amd.h)
   bool on_host = false;                  // host-resident: streamed tile by tile
   const uint64_t *pub_seeds = nullptr;   // [n] public seeds: the vectors are compact, c0 only (seeded.h)
+};
+// A coefficient vector of an inner product given as a linear form instead of rows: vector[t] = sum_e lv_e[t] * r_{k_e}
+// (slot-wise), lv_e[t] = Lcols[(col_e * L + limb) * Mlen + t] slot-constant scalars and r_0 = 1, r_k = k-th ring element of
+// `rings` -- the io vectors of the witness map (witness.hip, "io vectors without interpolation").  The plaintext of such a
+// vector is the same linear form of the PLAINTEXTS of the r_k (the inverse transform is linear over Z_q), so the inner
+// product never materialises the rows nor transforms them: P = batch-encoded [1, r_1, ..] as [(nk)][L][N_enc] canonical words.
+struct MsmLin {
+  const int *k = nullptr, *col = nullptr;  // device arrays [count]
+  int count = 0;
+  const double *Lcols = nullptr;
+  size_t Mlen = 0;
+  const uint64_t *P = nullptr;
+  unsigned long long T = 0;  // terms
 };
 // msm.hip.  msm_run: the caller holds the context's WsScope
 void msm_run(rs_ctx *ctx, const MsmKey &key, const rs_msm_vec *vecs, int n_vecs, int n_groups, uint64_t *d_out,

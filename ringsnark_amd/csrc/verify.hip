@@ -422,7 +422,7 @@ static void io_eval_at(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uint
   RS_REQUIRE(cs->m >= 1, "empty constraint system");
   uint64_t *const outs[3] = {d_Aio, d_Bio, d_Cio};
   WsScope ws_scope(ctx, st);
-  RS_DISPATCH_ARITH(ctx, (io_eval_run<Mod>(ctx, cs, d_s, outs, d_Zt, st)), (io_eval_run<ModI>(ctx, cs, d_s, outs, d_Zt, st)));
+  dispatch_arith(ctx, [&](auto tag) { io_eval_run<decltype(tag)>(ctx, cs, d_s, outs, d_Zt, st); });
 }
 
 static void vk_free(VkBase *vk) {
@@ -519,9 +519,9 @@ static void verify(rs_ctx *ctx, int K_lvl, const VkBase *cvk, const uint64_t *d_
     RS_HIP(hipMemsetAsync(vk->rep, 0, sizeof(h), st));
     RS_HIP(hipMemsetAsync(vk->rep, 0xFF, sizeof(unsigned long long), st));
     if (SCHEME == 0)
-      RS_DISPATCH_ARITH(ctx, (verify_run<Mod, 0>(ctx, a, vk->rep, st)), (verify_run<ModI, 0>(ctx, a, vk->rep, st)));
+      dispatch_arith(ctx, [&](auto tag) { verify_run<decltype(tag), 0>(ctx, a, vk->rep, st); });
     else
-      RS_DISPATCH_ARITH(ctx, (verify_run<Mod, 1>(ctx, a, vk->rep, st)), (verify_run<ModI, 1>(ctx, a, vk->rep, st)));
+      dispatch_arith(ctx, [&](auto tag) { verify_run<decltype(tag), 1>(ctx, a, vk->rep, st); });
     RS_HIP(hipMemcpyAsync(h, vk->rep, sizeof(h), hipMemcpyDeviceToHost, st));
     RS_HIP(hipStreamSynchronize(st));
   }

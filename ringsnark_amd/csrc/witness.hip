@@ -155,14 +155,13 @@ void r1cs_evaluate_run(rs_ctx *ctx, const rs_r1cs *cs, int which, int mode, cons
                        hipStream_t st) {
   const size_t S = ctx->ring_words();
   const unsigned by = (unsigned)((S / 2 + 255) / 256);
-  if (ctx->use_int)
-    hipLaunchKernelGGL(r1cs_eval_kernel<ModI>, dim3((unsigned)cs->m, by), dim3(256), 0, st, cs->d_row_ptr[which], cs->d_col[which],
-                       reinterpret_cast<const uint64_t *>(cs->d_coeff[which]), cs->nnz[which], d_asg, d_out, ctx->N, ctx->L, mode,
-                       (unsigned)cs->n_inputs, ctx->d_qmod_i, cs->d_pidx[which], reinterpret_cast<const uint64_t *>(cs->d_ptab));
-  else
-    hipLaunchKernelGGL(r1cs_eval_kernel<Mod>, dim3((unsigned)cs->m, by), dim3(256), 0, st, cs->d_row_ptr[which], cs->d_col[which],
-                       cs->d_coeff[which], cs->nnz[which], d_asg, d_out, ctx->N, ctx->L, mode, (unsigned)cs->n_inputs, ctx->d_qmod,
-                       cs->d_pidx[which], cs->d_ptab);
+  dispatch_arith(ctx, [&](auto tag) {  // rs_r1cs holds the table constants of either arithmetic behind double pointers
+    using M = decltype(tag);
+    using T = typename ArithOf<M>::T;
+    hipLaunchKernelGGL(r1cs_eval_kernel<M>, dim3((unsigned)cs->m, by), dim3(256), 0, st, cs->d_row_ptr[which], cs->d_col[which],
+                       reinterpret_cast<const T *>(cs->d_coeff[which]), cs->nnz[which], d_asg, d_out, ctx->N, ctx->L, mode,
+                       (unsigned)cs->n_inputs, CtxArith<M>::qmod(ctx), cs->d_pidx[which], reinterpret_cast<const T *>(cs->d_ptab));
+  });
   RS_HIP(hipGetLastError());
 }
 
@@ -422,8 +421,7 @@ static void witness_run_arith(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_
 void witness_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_asg, const uint64_t *d1, const uint64_t *d2,
                  const uint64_t *d3, uint64_t *const outs[7], uint64_t *h_Z, hipStream_t st, int slot0, int nslots, bool compact,
                  const size_t (*rows)[2]) {
-  RS_DISPATCH_ARITH(ctx, (witness_run_arith<Mod>(ctx, cs, d_asg, d1, d2, d3, outs, h_Z, st, slot0, nslots, compact, rows)),
-                    (witness_run_arith<ModI>(ctx, cs, d_asg, d1, d2, d3, outs, h_Z, st, slot0, nslots, compact, rows)));
+  dispatch_arith(ctx, [&](auto tag) { witness_run_arith<decltype(tag)>(ctx, cs, d_asg, d1, d2, d3, outs, h_Z, st, slot0, nslots, compact, rows); });
 }
 
 template <class M_>
@@ -602,7 +600,7 @@ int rs_interpolate(rs_ctx *ctx, const uint64_t *d_y, uint64_t *d_out, size_t n, 
   RS_API_BEGIN_CTX(ctx)
   RS_REQUIRE(ctx && d_y && d_out && n >= 1, "null argument");
   WsScope ws_scope(ctx, S(stream));
-  RS_DISPATCH_ARITH(ctx, (interpolate_arith<Mod>(ctx, d_y, d_out, n, S(stream))), (interpolate_arith<ModI>(ctx, d_y, d_out, n, S(stream))));
+  dispatch_arith(ctx, [&](auto tag) { interpolate_arith<decltype(tag)>(ctx, d_y, d_out, n, S(stream)); });
   RS_API_END
 }
 
