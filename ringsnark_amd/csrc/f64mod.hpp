@@ -10,7 +10,16 @@
 //     r = fma(-k, p, h) + l                 =>  r = a*b - k*p          (exact, |r| <= 0.75 p)
 //
 // valid whenever |a*b| <= p * 2^49 (then 3*eps*|a*b/p| <= 1/4, |r| < 2^53 and both the fma and
-// the final add are exact because their results are integers below 2^53).  All values are held
+// the final add are exact because their results are integers below 2^53).
+//
+// Second regime, |a*b| <= p * 2^50: what the kernels meet at primes in [2^49, 2^50) -- two canonical residues
+// (|a*b| < p^2), an inverse butterfly's difference after a reduction times a twiddle (1.02 p * p/2), a canonical residue
+// times a centred one.  There |a*b/p| <= 2^50, so |k - a*b/p| <= 1/2 + 3*2^-53*2^50 = 0.875 and |r| <= 0.875 p < 2^50;
+// h - k*p = r - l is still an integer below 2^53 (|l| <= 2^47), so the fma and the add stay exact and the value is
+// right.  Only the magnitude bound is wider: four such products sum to at most 3.5 p < 2^52, reduce()'s limit.
+// tests/f64mod_check.cpp checks both regimes, the second without skipping any operand pair.
+//
+// All values are held
 // as signed ("balanced") integers in doubles; callers keep |v| <= 2^50 (mul operand) and
 // |v| <= 2^52 (add operand).  Canonicalisation maps to [0, p).  Bit-exactness against a 128-bit
 // integer reference is asserted in tests/test_f64mod.py (CPU) and in every GPU parity test.
@@ -46,7 +55,7 @@ RS_HD double f64_fma(double a, double b, double c) {
 #endif
 }
 
-// a*b mod p, |result| <= 0.75p.  Requires |a*b| <= p*2^49.
+// a*b mod p, |result| <= 0.75p.  Requires |a*b| <= p*2^49 (second regime: |a*b| <= p*2^50 gives |result| <= 0.875p).
 RS_HD double mulmod(double a, double b, const Mod &m) {
   double h = a * b;
   double l = f64_fma(a, b, -h);

@@ -191,6 +191,8 @@ def preset(name: str) -> RingParams:
         return make_params(32, [43, 44], 64, [43, 44, 44], ring_factor=1 << 23, name="toy44x")
     if name == "toy44":  # small ring, headline-size primes (= 1 mod 2^20): large-m witness-map tests
         return make_params(32, [43, 44], 64, [43, 44, 44], ring_factor=1 << 20, name="toy44")
-    if name == "toy49":  # stresses the 50-bit bound of the FP64 modmul path
+    if name == "toy49":  # 49-bit primes (below 2^49): inside the first regime of the FP64 modmul (f64mod.hpp) for canonical operands
         return make_params(64, [49, 49], 128, [49, 49, 49], ring_factor=1 << 12, name="toy49")
+    if name == "toy50":  # toy49's shape on primes just below 2^50, the largest the FP64 arithmetic accepts (f64mod.hpp's second regime)
+        return make_params(64, [50, 50], 128, [50, 50, 50], ring_factor=1 << 12, name="toy50")
     raise KeyError(name)

@@ -68,6 +68,33 @@ int main(int argc, char **argv) {
         const double want = rs::center((double)imod((i128)a, p), m);
         expect(rs::center_balanced((double)a, m) == want, "center_balanced at a boundary");
       }
+    // Second regime (f64mod.hpp): |a*b| <= p * 2^50, the operand classes the kernels really multiply.  Nothing is skipped:
+    // every pair below is inside it for every p < 2^50, and for p > 2^49 most are outside the first regime.
+    const int64_t ip = (int64_t)p, hp = (int64_t)(p / 2), wide = (int64_t)(p + p / 50);  // wide = floor(1.02 p)
+    for (int it = 0; it < 2000000; it++) {
+      uint64_t ra = sm(st), rb = sm(st);
+      int64_t a, b;
+      switch (it % 10) {
+        case 0: a = (int64_t)(ra % p); b = (int64_t)(rb % p); break;                                  // (a) canonical x canonical
+        case 1: a = ip - 1 - (int64_t)(ra & 1023); b = ip - 1 - (int64_t)(rb & 1023); break;          // (a) both within 1024 of p - 1
+        case 2: a = ip - 1 - (int64_t)(ra & 1023); b = (int64_t)(rb % p); break;                      // (a) one at the top
+        case 3: a = (int64_t)(ra % (uint64_t)(2 * wide + 1)) - wide; b = (int64_t)(rb % p) - hp; break;  // (b) |a| <= 1.02 p, |b| <= p/2
+        case 4: a = wide - (int64_t)(ra & 1023); b = hp - (int64_t)(rb & 1023); break;                // (b) the corners, all four signs
+        case 5: a = -wide + (int64_t)(ra & 1023); b = hp - (int64_t)(rb & 1023); break;
+        case 6: a = wide - (int64_t)(ra & 1023); b = -hp + (int64_t)(rb & 1023); break;
+        case 7: a = -wide + (int64_t)(ra & 1023); b = -hp + (int64_t)(rb & 1023); break;
+        case 8: a = (int64_t)(ra % p); b = (int64_t)(rb % p) - hp; break;                             // (c) canonical x centred
+        default: a = ip - 1 - (int64_t)(ra & 1023);                                                   // (c) both at their ends
+                 b = ((rb >> 20) & 1) ? hp - (int64_t)(rb & 1023) : -hp + (int64_t)(rb & 1023); break;
+      }
+      const i128 prod = (i128)a * b;
+      const i128 bound = (i128)p << 50;
+      expect(prod <= bound && -prod <= bound, "second regime: operands inside |a*b| <= p * 2^50");
+      const double r = rs::mulmod((double)a, (double)b, m);
+      expect(r == (double)(int64_t)r, "second regime: mulmod integral");
+      expect(imod((i128)(int64_t)r, p) == imod(prod, p), "second regime: mulmod value");
+      expect(r <= 0.875 * (double)p + 1 && r >= -0.875 * (double)p - 1, "second regime: mulmod bound");
+    }
   }
   if (fails) { fprintf(stderr, "%lld failures\n", fails); return 1; }
   printf("ok\n");

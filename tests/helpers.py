@@ -149,7 +149,10 @@ def aligned_terms(ctx, D, seed, frac=0.30, kinds=None, slot_const=False, rings=N
     3 * 2^-4 = 0.1875.  a b / p = integer + target / p with |target / p| <= 0.30, and 0.30 + 0.1875 < 0.5: the rounded
     quotient is that integer and the kernel's product is exactly `target`, whichever lazy representative of u it holds.
     The expected sum therefore needs no oracle (closed_form), and an accumulator that is never reduced holds exactly the
-    running sum of the targets."""
+    running sum of the targets.  Primes in [2^49, 2^50) (the *q50 contexts, toy50): with a centred b (|b| <= p / 2) the same
+    holds; with a lazier representative, |b| up to p, the error bound is 0.375 and a product may come out as target -+ p
+    (f64mod.hpp's second regime, |r| <= 0.875 p).  It is the same residue, so closed_form is still the expected value, and
+    what makes the sums large is the condition check_aligned_inputs asserts on the targets."""
     if rings is None:
         if slot_const:
             rng = np.random.RandomState(seed + 1)
@@ -250,7 +253,17 @@ WORST_CASES = {
     "n8192q44": (8192, [43], 8192, [44]),
     "hybrid8192": (8192, [54], 8192, [49, 48]),
     "n16384full": (16384, [43], 16384, [49, 48]),  # N == N_enc at 16384 points: extreme plaintext rows
+    # the same kernel families on primes just below 2^50, the largest the FP64 arithmetic accepts: acc_period is 4 there
+    "toy50": None,
+    "n2048q50": (2048, [43], 2048, [50, 50]),
+    "n8192q50": (8192, [50], 8192, [50, 50]),  # N == N_enc: extreme rows of a 50-bit ring prime, +-2 (q - 1) is about 2^51
+    "n16384q50": (2048, [43], 16384, [50, 50]),
+    "hybrid8192q50": (8192, [54], 8192, [50, 50]),
 }
+# the order the seeds of aligned_case / extreme_case count in: names are only ever appended, so a case keeps its inputs
+_SEED_ORDER = ("hybrid8192", "n16384", "n16384full", "n2048", "n8192", "n8192q44", "toy49",
+               "toy50", "n2048q50", "n8192q50", "n16384q50", "hybrid8192q50")
+assert sorted(_SEED_ORDER) == sorted(WORST_CASES)
 ALIGNED_D = 8
 
 
@@ -270,7 +283,7 @@ def aligned_case(name, variant="poly", key=0):
         prm = worst_case_params(name)
         ctx = oracle_ctx(prm)
         T = aligned_T(prm.Q)
-        seed = 1000 + 16 * sorted(WORST_CASES).index(name) + ("poly", "one", "const").index(variant)
+        seed = 1000 + 16 * _SEED_ORDER.index(name) + ("poly", "one", "const").index(variant)
         kinds = np.full(ALIGNED_D, O.KIND_ONE, dtype=np.uint8) if variant == "one" else None
         rings = aligned_case(name, variant)[1] if key else None
         rings, encs, targets = aligned_terms(ctx, ALIGNED_D, seed + 8 * key, kinds=kinds, slot_const=variant == "const", rings=rings)
@@ -278,7 +291,7 @@ def aligned_case(name, variant="poly", key=0):
     return _ALIGNED[(name, variant, key)]
 
 
-EXTREME_CASES = {"n8192": 4, "hybrid8192": 1, "n16384full": 4}  # context -> vectors per group (MAX_GROUP_VECS; hybrid: one)
+EXTREME_CASES = {"n8192": 4, "hybrid8192": 1, "n16384full": 4, "n8192q50": 4}  # context -> vectors per group (MAX_GROUP_VECS; hybrid: one)
 
 
 def extreme_case(name):
@@ -290,7 +303,7 @@ def extreme_case(name):
         ctx = oracle_ctx(prm)
         n_vecs = EXTREME_CASES[name]
         rings = np.stack([np.stack([extreme_rows(ctx, i, EXTREME_PATTERNS[d % 4], seed=d) for i in range(ctx.L)]) for d in range(ALIGNED_D)])
-        _, encs, targets = aligned_terms(ctx, ALIGNED_D, 2000 + sorted(WORST_CASES).index(name), rings=[rings] * n_vecs)
+        _, encs, targets = aligned_terms(ctx, ALIGNED_D, 2000 + _SEED_ORDER.index(name), rings=[rings] * n_vecs)
         _ALIGNED[(name, "extreme")] = (ctx, rings, n_vecs, encs, targets, aligned_T(prm.Q))
     return _ALIGNED[(name, "extreme")]
 

@@ -9,7 +9,7 @@ from ringsnark_amd import modswitch as MS
 from ringsnark_amd import params as P
 from tests import helpers as H
 
-PRESETS = ("toy", "toyR", "toy49", "toy54", "toy60")
+PRESETS = ("toy", "toyR", "toy49", "toy50", "toy54", "toy60")
 KINDS = ("fresh", "product")
 COUNT = 2  # encoding elements per (preset, kind)
 

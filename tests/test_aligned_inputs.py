@@ -8,11 +8,11 @@ from ringsnark_amd import params as P
 from tests import helpers as H
 
 
-@pytest.mark.parametrize("name", ["toy49", "n2048"])
+@pytest.mark.parametrize("name", ["toy49", "n2048", "toy50", "n2048q50"])
 def test_closed_form_equals_the_oracle_inner_product(name):
     """sum_d count_d target_d mod Q_j is what EncodingElem::inner_product gives on the aligned terms, bit for bit: ring
-    elements, an all-KIND_ONE vector, a second key for the same rows, and (toy49) a slot-constant vector as expanded rows."""
-    variants = (("poly", 0), ("one", 0), ("poly", 1), ("const", 0), ("const", 1)) if name == "toy49" else (("poly", 0),)
+    elements, an all-KIND_ONE vector, a second key for the same rows, and (toy49, toy50) a slot-constant vector as expanded rows."""
+    variants = (("poly", 0), ("one", 0), ("poly", 1), ("const", 0), ("const", 1)) if name in ("toy49", "toy50") else (("poly", 0),)
     for variant, key in variants:
         ctx, rings, encs, targets, T, kinds = H.aligned_case(name, variant, key)
         assert T == H.aligned_T(ctx.Q) and encs.shape == targets.shape == ctx.enc_shape(H.ALIGNED_D)
@@ -27,7 +27,8 @@ def test_aligned_T_is_a_handful_of_accumulator_periods():
     """ceil(2^53 / (0.30 min Q - 2^20)) + margin: about 107 + 4 terms at 48 bits, 1707 + 4 at 44 bits."""
     assert H.aligned_T([(1 << 48) - 1, (1 << 49) - 1]) == 107 + 4
     assert H.aligned_T([1 << 44], margin=9) == 1707 + 9
-    for bits in (40, 44, 48, 49):
+    assert H.aligned_T([(1 << 50) - 27]) == 27 + 4
+    for bits in (40, 44, 48, 49, 50):
         Q = (1 << bits) - 1
         T = H.aligned_T([Q])
         assert (T - 4) * (0.30 * Q - 2**20) >= 2**53 > (T - 5) * (0.30 * Q - 2**20)
@@ -37,7 +38,7 @@ def test_aligned_T_is_a_handful_of_accumulator_periods():
 def test_every_slab_of_every_case_leaves_the_exact_integers(name):
     """Per (limb, component, prime) slab of every GPU case, with the case's own T: every |target| <= 0.30 Q_j, one sign per
     slab, both signs in the call, and the never-reduced running sum beyond 2^53 at some position."""
-    variants = (("poly", 0), ("one", 0), ("const", 0), ("poly", 1)) if name == "toy49" else (("poly", 0),)
+    variants = (("poly", 0), ("one", 0), ("const", 0), ("poly", 1)) if name in ("toy49", "toy50") else (("poly", 0),)
     for variant, key in variants:
         ctx, rings, encs, targets, T, kinds = H.aligned_case(name, variant, key)
         assert H.check_aligned_inputs(ctx, targets, T) > 1.0

@@ -105,6 +105,7 @@ def batch_case(name, scheme, m, zk, oracle_sk=True):
 
 
 TOY_CASES = [("toy", "groth16", False), ("toy", "rinocchio", True), ("toy49", "groth16", False), ("toy49", "rinocchio", False),
+             ("toy50", "groth16", False), ("toy50", "rinocchio", False),
              ("toy60", "groth16", False), ("toy60", "rinocchio", False)]
 
 

@@ -22,7 +22,7 @@ from ringsnark_amd import r1cs as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "ringsnark_amd", "bits.h")
-PRESETS = ("toy", "toy49", "toy60", "toy54")  # FP64 context L = 2; N = 64; integer context; L = 1 (no second limb to compare)
+PRESETS = ("toy", "toy49", "toy50", "toy60", "toy54")  # FP64 context L = 2; N = 64; primes just below 2^50; integer context; L = 1 (no second limb to compare)
 FIELDS = ("n_bad", "first_elem", "first_limb", "first_slot", "word", "value")
 SENTINEL = 0xA5A5A5A5A5A5A5A5
 PIECE_PAIRS = 2048  # csrc/bits.hip BITS_PIECE: slot pairs of a piece

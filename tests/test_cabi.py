@@ -35,10 +35,14 @@ def test_ctx_create_fails_loudly_without_gpu():
 
 
 def test_presets_are_consistent():
-    for name in ("C1", "C2", "C3", "C3F", "C4", "C4F", "C5", "C5s", "toy", "toy49", "toyC3"):
+    for name in ("C1", "C2", "C3", "C3F", "C4", "C4F", "C5", "C5s", "toy", "toy49", "toy50", "toyC3"):
         prm = P.preset(name).validate()
         if name != "C5":  # BFVDefault(2048) is one 54-bit prime: the integer (Montgomery) arithmetic
             assert all(p < (1 << 50) for p in prm.q + prm.Q)
+    t50 = P.preset("toy50")  # the top of the FP64 range: every prime in [2^49, 2^50), within 2^-33 of the limit
+    assert t50.q == [0x3FFFFFFFE5001, 0x3FFFFFFFFC001] and t50.Q == [0x3FFFFFFFFB201, 0x3FFFFFFFFBB01, 0x3FFFFFFFFF901]
+    assert all(p > 0.9999999999 * 2**50 for p in t50.q + t50.Q)
+    assert all(p < (1 << 49) for p in P.preset("toy49").q + P.preset("toy49").Q)
     c3 = P.preset("C3")
     assert (c3.N, c3.L, c3.N_enc, c3.K) == (8192, 4, 8192, 4)
     # q_i = default_double_batching_modulus(8192, 8192) = CoeffModulus::Create(8192, {43, 43, 44, 44}) -- the

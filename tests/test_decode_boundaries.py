@@ -21,9 +21,9 @@ from ringsnark_amd import params as P
 from tests import helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["toy", "toy49", "toy54", "toy60"]  # every threshold row; toy / toy49: FP64, toy54 / toy60: the integer (Montgomery) arithmetic
+SMALL = ["toy", "toy49", "toy50", "toy54", "toy60"]  # every threshold row; toy / toy49 / toy50: FP64, toy54 / toy60: the integer (Montgomery) arithmetic
 BIG = ["C2", "C5"]                          # the reduced rows; C2: FP64, 8 coefficients per thread, C5: integer, 16
-KERNEL = {"toy": "crt_decode_kernel", "toy49": "crt_decode_kernel", "C2": "crt_decode_kernel",
+KERNEL = {"toy": "crt_decode_kernel", "toy49": "crt_decode_kernel", "toy50": "crt_decode_kernel", "C2": "crt_decode_kernel",
           "toy54": "crt_decode_kernel_int", "toy60": "crt_decode_kernel_int", "C5": "crt_decode_kernel_int"}
 LIMB_STEP = 7  # limb i of element e of a sweep carries value e + 7 i of the list: no two limbs of an element hold the same value
 
@@ -440,7 +440,7 @@ def test_verifier_accepts_one_bit_of_budget_and_refuses_none(scheme):
 
 
 # ---- the encode side: the centred lift at its boundary ---------------------------------------------------------------------
-LIFT_PRESETS = ["toy49", "toy60"]  # FP64 (center) and integer (lift_centered) arithmetic
+LIFT_PRESETS = ["toy49", "toy50", "toy60"]  # FP64 (center) and integer (lift_centered) arithmetic
 LIFT_PER_C = 12
 M64 = (1 << 64) - 1
 

@@ -62,7 +62,7 @@ def _budget_ladder(ctx, sk, seed=3):
     return np.stack(out), r
 
 
-@pytest.mark.parametrize("name", ["toy", "toy49", "toy60", "C2"])
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "toy60", "C2"])
 def test_oracle_noise_budget_and_guard(name):
     """CPU: Decryptor::invariant_noise_budget restated (SEAL 4.x, bgv: || c0 + c1 s mod Q ||_inf centred, no scaling by t)
     and the guard of EncodingElem::decode (seal_ring.tcc:443-454).  Fresh: bit_count(Q) - log2(t |e| N-ish) - 1; every
@@ -97,7 +97,7 @@ def test_oracle_noise_budget_and_guard(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["toy", "toy49", "C2", "toy54", "toy60", "C5"])  # toy54 / toy60 / C5 (ring side): integer arithmetic
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "C2", "toy54", "toy60", "C5"])  # toy50: the top of the FP64 range; toy54 / toy60 / C5 (ring side): integer arithmetic
 def test_noise_budget_and_decode_guard_match_oracle(name):
     """rs_enc_noise_budget equals the oracle's budget for every ciphertext of the ladder (both arithmetics; the device
     finds the bit length by digit comparisons in mixed radix, the oracle composes multi-word integers), and rs_enc_decode
@@ -137,7 +137,7 @@ def test_noise_budget_and_decode_guard_match_oracle(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["toy", "toy49", "C2", "toy54", "toy60"])  # toy54 / toy60: the integer (Montgomery) arithmetic
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "C2", "toy54", "toy60"])  # toy54 / toy60: the integer (Montgomery) arithmetic
 def test_enc_encode_decode_match_oracle(name):
     from ringsnark_amd.device import Device, to_host
     prm = P.preset(name)
@@ -159,6 +159,30 @@ def test_enc_encode_decode_match_oracle(name):
     assert (d == ctx.enc_decode(sk, ip)).all()
     want = ctx.ring_add(ctx.ring_mul(rings[0], r2[0]), ctx.ring_mul(rings[2], r2[2]))
     assert (d == want).all()  # homomorphism: decode(<E(a), b>) = <a, b>
+
+
+@pytest.mark.gpu
+def test_toy50_runs_the_fp64_kernels():
+    """Arithmetic selection at the top of the accepted range: every prime of toy50 is in [2^49, 2^50), the context is not on
+    the integer arithmetic, and the profile of an encode + decode names the FP64 kernels, none with the _int suffix."""
+    from ringsnark_amd.device import Device, to_host
+    prm = P.preset("toy50")
+    assert all(1 << 49 <= p < 1 << 50 for p in prm.q + prm.Q)
+    dev, ctx = Device(prm), H.oracle_ctx(prm)
+    sk = ctx.keygen(3)
+    rings = ctx.random_ring(41, 2)
+    dsk, drings = dev.put(sk), dev.put(rings)
+    dev.set_profiling(True)
+    try:
+        dev.profile_read()
+        dec = to_host(dev.enc_decode(dsk, dev.enc_encode(dsk, drings, 9)))
+        names = {k["name"] for k in dev.profile_read()}
+    finally:
+        dev.set_profiling(False)
+    assert (dec == rings).all()
+    assert {k for k in names if k.startswith("crt_decode_kernel")} == {"crt_decode_kernel"}, names
+    assert {k for k in names if k.startswith("decrypt_dot_kernel")} == {"decrypt_dot_kernel"}, names
+    assert not any("_int" in k for k in names), names
 
 
 @pytest.mark.gpu
@@ -301,7 +325,7 @@ def test_wire_format_roundtrip_and_validation():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,m,kind", [("toy", 6, "chain"), ("toy49", 11, "wide"), ("toy54", 9, "wide"), ("toy60", 7, "chain"),
+@pytest.mark.parametrize("name,m,kind", [("toy", 6, "chain"), ("toy49", 11, "wide"), ("toy50", 11, "wide"), ("toy54", 9, "wide"), ("toy60", 7, "chain"),
                                          ("toy", 9, "wide_poly"), ("toy60", 7, "wide_poly")])
 def test_instance_map_with_evaluation_matches_restatement(name, m, kind):
     """At/Bt/Ct/Ht/Zt on the device against the O(m^2) restatement of

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_f64mod_exact_against_int128():
     primes = set()
-    for name in ("toy", "toy49", "C2", "C3", "C4"):
+    for name in ("toy", "toy49", "toy50", "C2", "C3", "C4"):
         prm = P.preset(name)
         primes.update(prm.q + prm.Q)
     primes.add((1 << 50) - 27)  # largest prime below 2^50: the documented limit

@@ -16,6 +16,11 @@ pytestmark = pytest.mark.gpu
 _DEV = {}
 
 
+def _params(name):
+    """A preset, or one of the custom contexts of tests/helpers.py (WORST_CASES: the 50-bit primes at 8192 and 16384 points)"""
+    return H.worst_case_params(name) if name in H.WORST_CASES and H.WORST_CASES[name] is not None else P.preset(name)
+
+
 def dev_for(name):
     """Device per preset.  "<preset>+int": the same preset on the integer (Montgomery) arithmetic, which contexts
     otherwise select only when a modulus is >= 2^50 (tuning knob force_int_arith, read at context creation)."""
@@ -23,7 +28,7 @@ def dev_for(name):
     if name not in _DEV:
         base, force = (name[:-4], True) if name.endswith("+int") else (name, False)
         with _lib.tuning(**(dict(force_int_arith=1) if force else {})):
-            _DEV[name] = Device(P.preset(base))
+            _DEV[name] = Device(_params(base))
     return _DEV[name]
 
 
@@ -32,7 +37,7 @@ def host(t):
     return to_host(t)
 
 
-@pytest.mark.parametrize("name", ["toy", "toy49", "C2", "C3", "C5s", "C4", "toy54", "toy60", "micro60", "C5", "toy+int", "toy49+int"])
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "C2", "C3", "C5s", "C4", "toy54", "toy60", "micro60", "C5", "toy+int", "toy49+int"])
 def test_ntt_matches_oracle(name):
     dev = dev_for(name)
     prm = dev.prm
@@ -59,7 +64,7 @@ _NTT_STRUCTURED = {}
 def _structured_ntt_cases(name):
     """[(modset, index, inputs [7][n], forward [7][n], inverse [7][n])] per prime of the preset, oracle side, built once."""
     if name not in _NTT_STRUCTURED:
-        prm = P.preset(name)
+        prm = _params(name)
         n, logn = prm.N_enc, prm.N_enc.bit_length() - 1
         sets = ((_lib.RS_MOD_PLAIN, prm.q), (_lib.RS_MOD_COEFF, prm.Q)) if name != "C5s" else ((_lib.RS_MOD_COEFF, prm.Q),)
         out = []
@@ -80,12 +85,14 @@ def _structured_ntt_cases(name):
 @pytest.mark.parametrize("batch", [1, 3])
 @pytest.mark.parametrize("variant", [0, 12, 14])
 @pytest.mark.parametrize("inverse", [False, True])
-@pytest.mark.parametrize("name", ["toy49", "C2", "C5s"])
+@pytest.mark.parametrize("name", ["toy49", "toy50", "C2", "n8192q50", "C5s", "n16384q50"])
 def test_ntt_structured_inputs_match_oracle(name, inverse, variant, batch):
     """The standalone transforms on inputs where an error cannot average out: all p - 1, all (p - 1) / 2, alternating
     0, p - 1, and a unit impulse at 0, 1, n / 2 and n - 1 -- its transform is a row of twiddles, so a wrong table index is a
     wrong value.  128, 8192 and 16384 points (C5s: the data primes), both directions, the barrier, wave-private and wide
-    kernels (ntt_variant 0, 12, 14), one polynomial per launch and three."""
+    kernels (ntt_variant 0, 12, 14), one polynomial per launch and three.  toy50, n8192q50, n16384q50: the same sizes on
+    primes just below 2^50, where the reduction masks allow no stage without a reduction (lim = 2^50 / p is about 1) and
+    all p - 1 and alternating 0, p - 1 sit on the bounds the masks are built for."""
     dev = dev_for(name)
     with _lib.tuning(ntt_variant=variant):
         for modset, idx, a, fwd, inv in _structured_ntt_cases(name):
@@ -133,7 +140,7 @@ def test_ntt_variants_select_three_kernels_with_equal_results():
             assert kernels[8] == kernels[12] and kernels[14] != kernels[8] and kernels[0] != kernels[8], kernels
 
 
-@pytest.mark.parametrize("name", ["toy", "toy49", "C2", "toy54", "toy60", "micro60", "toy+int"])
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "C2", "toy54", "toy60", "micro60", "toy+int"])
 def test_ring_ops_match_oracle(name):
     dev = dev_for(name)
     ctx = H.oracle_ctx(dev.prm)
@@ -158,7 +165,7 @@ def test_ring_ops_match_oracle(name):
     assert ei.value.code == RS_ERR_NOT_INVERTIBLE and "not invertible in ring" in str(ei.value)
 
 
-@pytest.mark.parametrize("name", ["toy", "toy49", "C2", "toy54", "toy60", "toy49+int"])
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "C2", "toy54", "toy60", "toy49+int"])
 def test_batch_encode_and_enc_ops(name):
     dev = dev_for(name)
     ctx = H.oracle_ctx(dev.prm)
@@ -175,7 +182,7 @@ def test_batch_encode_and_enc_ops(name):
     assert (host(dev.enc_add(de[0], de[1])) == ctx.enc_add(e[0], e[1])).all()
 
 
-@pytest.mark.parametrize("name,T", [("toy", 1), ("toy", 37), ("toy49", 50), ("C2", 5), ("toy54", 37), ("toy60", 50), ("C5", 3),
+@pytest.mark.parametrize("name,T", [("toy", 1), ("toy", 37), ("toy49", 50), ("toy50", 50), ("C2", 5), ("toy54", 37), ("toy60", 50), ("C5", 3),
                                     ("toy+int", 37), ("toy49+int", 20), ("C4", 5), ("C5s", 40)])
 def test_inner_product_matches_oracle(name, T):
     dev = dev_for(name)
@@ -377,6 +384,7 @@ def test_wide_kernels_equal_their_predecessors_and_the_oracle(name):
                                           ("toy", 16, "wide"), ("toy", 100, "wide"), ("toy", 100, "many_inputs"),
                                           ("toy", 600, "wide"),  # M = 1024: split Newton / in-place product-tree kernels
                                           ("toy49", 33, "wide"), ("toy49", 64, "chain"), ("toy49", 90, "many_inputs"),
+                                          ("toy50", 33, "wide"), ("toy50", 64, "chain"), ("toy50", 90, "many_inputs"),  # primes just below 2^50
                                           # primes >= 2^50: the integer (Montgomery) arithmetic, generic kernels
                                           ("toy54", 1, "chain"), ("toy54", 7, "wide"), ("toy54", 100, "wide"), ("toy54", 100, "many_inputs"),
                                           ("toy60", 16, "wide"), ("toy60", 64, "chain"), ("toy60", 600, "wide"), ("toy60", 90, "many_inputs"),
@@ -413,7 +421,7 @@ def test_witness_map_matches_oracle(name, m, kind):
 
 
 @pytest.mark.parametrize("name,m,aux_only,zk,lds", [("toy", 9, False, True, 13), ("toy", 12, True, True, 13), ("toy60", 9, False, False, 13),
-                                                     ("toy+int", 12, True, True, 13), ("toy49", 150, False, True, 6), ("toy", 150, True, False, 6),
+                                                     ("toy+int", 12, True, True, 13), ("toy49", 150, False, True, 6), ("toy50", 150, False, True, 6), ("toy", 150, True, False, 6),
                                                      ("toy54", 70, False, True, 6)])
 def test_polynomial_coefficients_match_oracle(name, m, aux_only, zk, lds):
     """Row a14 with coefficients that are general ring elements (rs_r1cs_create_poly; relations/variable.tcc:246-254,
@@ -534,7 +542,7 @@ def test_interpolate_known_answer_on_device():
         assert (got[k] == k).all()
 
 
-@pytest.mark.parametrize("name,m,kind", [("toy", 6, "wide"), ("toy", 16, "chain"), ("toy49", 21, "wide"), ("toy54", 12, "wide"),
+@pytest.mark.parametrize("name,m,kind", [("toy", 6, "wide"), ("toy", 16, "chain"), ("toy49", 21, "wide"), ("toy50", 21, "wide"), ("toy54", 12, "wide"),
                                           ("toy60", 21, "wide"), ("toy+int", 16, "chain")])
 def test_groth16_prover_matches_oracle(name, m, kind):
     dev = dev_for(name)
@@ -550,7 +558,7 @@ def test_groth16_prover_matches_oracle(name, m, kind):
     assert (host(got) == exp).all()
 
 
-@pytest.mark.parametrize("name,m,zk", [("toy", 5, False), ("toy", 12, True), ("toy49", 16, True), ("toy54", 9, True), ("toy60", 12, True),
+@pytest.mark.parametrize("name,m,zk", [("toy", 5, False), ("toy", 12, True), ("toy49", 16, True), ("toy50", 16, True), ("toy54", 9, True), ("toy60", 12, True),
                                        ("toy60", 5, False)])
 def test_rinocchio_prover_matches_oracle(name, m, zk):
     dev = dev_for(name)
@@ -880,7 +888,7 @@ def test_witness_map_row_ranges_equal_slices_of_the_whole(name, m, kind, zk):
     assert (host(sub["A_mid"]) == full["A_mid"][3:9]).all() and (host(sub["H"]) == full["H"][1:]).all() and sub["B_mid"] is None
 
 
-@pytest.mark.parametrize("name,T", [("toy", 9), ("toy49", 20), ("toy60", 9), ("C2", 6), ("C5s", 4), ("C4", 3), ("C5", 5)])
+@pytest.mark.parametrize("name,T", [("toy", 9), ("toy49", 20), ("toy50", 20), ("toy60", 9), ("C2", 6), ("C5s", 4), ("C4", 3), ("C5", 5)])
 def test_slot_constant_vectors_equal_their_expanded_rows(name, T):
     """rs_msm_vec::slot_const: a vector whose ring elements hold one value per limb in every slot (coefficients_for_Z,
     util/evaluation_domain.tcc:54-60) handed over as the compact [T][L] array of values -- the plaintext is value x
@@ -1117,7 +1125,7 @@ def test_multipass_production_tile_matches_oracle_on_a_few_slots():
             assert (host(w[k])[:, limb, :] == exp[k]).all(), (k, limb)
 
 
-@pytest.mark.parametrize("name", ["toy", "toy49", "toy54", "toy60"])
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "toy54", "toy60"])
 def test_poly_multiply_add_divide_match_oracle(name):
     """Row a11 (util/polynomials.tcc:62-81): per-slot polynomial product / sum / quotient with ring-element
     coefficients, non-monic per-slot divisors included, against the oracle's schoolbook restatement."""

@@ -30,7 +30,7 @@ def _case(preset, m, zk, poly=False, seed=3):
 
 
 @pytest.mark.parametrize("preset,m,zk,poly", [("toy", 1, False, False), ("toy", 5, False, False), ("toy", 12, True, False),
-                                              ("toy", 16, True, False), ("toy49", 33, True, False), ("toy60", 20, True, False),
+                                              ("toy", 16, True, False), ("toy49", 33, True, False), ("toy50", 33, True, False), ("toy60", 20, True, False),
                                               ("toy", 9, True, True)])
 def test_the_oracle_map_satisfies_every_identity_in_every_slot(preset, m, zk, poly):
     prm, ctx, cs, asg, ds = _case(preset, m, zk, poly)

@@ -41,6 +41,8 @@ def _host(t):
     ("toyR", 6, 0, 600, "wide", True),       # recipe primes as they come (2-adicity 7, 7)
     ("toy49", 6, 7, 300, "wide", True),      # 49-bit primes: the reductions inside the polynomial products matter
     ("toy", 6, 7, 300, "int", True),         # the FP64 primes on the integer arithmetic
+    ("toy50", 6, 7, 300, "wide", True),      # primes just below 2^50: three stages short, sums of 8 products inside inc_polymul
+    ("toy50", 6, 7, 600, "chain", False),    # four stages short, G = 16: the longest sums inside inc_polymul, reduced every 4 products
 ])
 def test_incomplete_transforms_match_oracle(name, lds, force, m, kind, zk):
     from ringsnark_amd.device import Device
@@ -145,7 +147,19 @@ def test_headline_primes_through_the_tuned_kernels(m, zk):
 @pytest.mark.parametrize("m,force,sub_log", [(40000, 14, 12), (40000, 15, 13), (65536, 14, 13), (65536, 16, 12), (131072, 14, 12), (131072, 15, 12)])
 def test_incomplete_transforms_equal_complete_ones(m, force, sub_log):
     """Forced on primes that have the roots (toy44: = 1 mod 2^20): bit-equal to the complete transforms, on blocks of 2^12 and 2^13."""
-    prm = P.preset("toy44")
+    _forced_incomplete_equals_complete(P.preset("toy44"), m, force, sub_log)
+
+
+@pytest.mark.parametrize("m,force,sub_log", [(40000, 14, 12), (131072, 14, 12)])
+def test_incomplete_transforms_equal_complete_ones_at_50_bits(m, force, sub_log):
+    """The same on 50-bit ring primes = 1 mod 2^20, all just below 2^50: the tuned sub_ntt_w*_kernel<., 3> and <., 4> with their
+    products of two canonical residues, where every stage of a transform is preceded by a reduction."""
+    prm = P.make_params(32, [50, 50], 64, [50, 50, 50], ring_factor=1 << 20)
+    assert all(1 << 49 < p < 1 << 50 and p % (1 << 20) == 1 for p in prm.q)
+    _forced_incomplete_equals_complete(prm, m, force, sub_log)
+
+
+def _forced_incomplete_equals_complete(prm, m, force, sub_log):
     dev, cs, asg, ds, w, names = _run_large(prm, m, True, witness_force_bc=force, witness_sub_log=sub_log)
     assert not any(n.startswith("bc") for n in names), names
     inc = (m - 1).bit_length() + 1 - force

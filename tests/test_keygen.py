@@ -27,8 +27,8 @@ from tests import snark_ref as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STRIDE = 1 << 40
-G16_CASES = [("toy", 6), ("toy49", 12), ("toy60", 6)]  # toy60: the integer (Montgomery) arithmetic
-RIN_CASES = [("toy49", 9, False), ("toy", 9, True), ("toy60", 9, False)]  # (preset, m, ZK elements set)
+G16_CASES = [("toy", 6), ("toy49", 12), ("toy50", 12), ("toy60", 6)]  # toy60: the integer (Montgomery) arithmetic
+RIN_CASES = [("toy49", 9, False), ("toy50", 9, False), ("toy", 9, True), ("toy60", 9, False)]  # (preset, m, ZK elements set)
 G16_VECTORS = ("s_pows", "delta_ts", "delta_mid", "alpha", "beta")
 RIN_VECTORS = ("s_pows", "alpha_s_pows", "beta_prods", "beta_rv_ts", "beta_rw_ts", "beta_ry_ts")
 VECTORS = {"groth16": G16_VECTORS, "rinocchio": RIN_VECTORS}
@@ -235,7 +235,7 @@ def assert_same_key(dev, scheme, got, exp):
 # ---- GPU -------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("scheme", ["groth16", "rinocchio"])
-@pytest.mark.parametrize("name", ["toy", "toy49", "toy60"])
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "toy60"])
 def test_key_bytes_match_the_cpu(name, scheme):
     """Every vector equals the oracle's encoding of the rows the reference's formulas give: m = 1, 2, 12, entries on the
     constant one and on inputs with an empty row, and no auxiliary variable at all (the third vector is NULL)."""

@@ -11,7 +11,7 @@ non-temporal instantiation, so a second grid-stride round exists there only.  RI
     pieces+tail       toy / toy+int / toy60, 100 elements   one piece + 1152 pairs in one launch, per-access limb
     full-grid         C2 / C2+int, 1023 elements            2046 pieces = the largest launch that is not non-temporal
     nt+round2         C2 / C2+int, 1100 elements            NT, 2200 pieces: 152 workgroups run a second round, uniform limb
-    nt+round2+tail    mid / mid60, 8801 elements            NT, 2200 pieces + 512 pairs, per-access limb
+    nt+round2+tail    mid / mid50 / mid60, 8801 elements            NT, 2200 pieces + 512 pairs, per-access limb
 add and mul run a second time with dst == a (the C entry point directly) at pieces+tail and nt+round2+tail.
 
 test_enc_add_on_every_stream_path -- enc_add_kernel<NT> (csrc/msm_mac.hpp), the same shape with the prime of a word in place
@@ -45,6 +45,7 @@ pytestmark = pytest.mark.gpu
 # contexts that are no preset: name -> make_params arguments
 CUSTOM = {
     "mid": (512, [43, 44], 512, [49, 48, 48]),    # 1024 ring words, 6144 encoding words per element; FP64 arithmetic
+    "mid50": (512, [50, 50], 512, [50, 50, 50]),  # the same shape on primes just below 2^50, the largest of the FP64 arithmetic
     "mid60": (512, [59, 60], 512, [60, 60, 59]),  # the same shape on the integer arithmetic
     "w12": (4096, [43], 4096, [49, 36]),
     "w13": (8192, [43], 8192, [49, 48]),
@@ -104,13 +105,13 @@ RING_SHAPES = {  # path -> (contexts, elements, what _stream_path must say)
     "pieces+tail": (("toy", "toy+int", "toy60"), 100, dict(pieces=1, tail=1152, nt=False, second_round=False, per_access=True)),
     "full-grid": (("C2", "C2+int"), 1023, dict(pieces=2046, tail=0, nt=False, second_round=False, per_access=False)),
     "nt+round2": (("C2", "C2+int"), 1100, dict(pieces=2200, tail=0, nt=True, second_round=True, per_access=False)),
-    "nt+round2+tail": (("mid", "mid60"), 8801, dict(pieces=2200, tail=512, nt=True, second_round=True, per_access=True)),
+    "nt+round2+tail": (("mid", "mid50", "mid60"), 8801, dict(pieces=2200, tail=512, nt=True, second_round=True, per_access=True)),
 }
 ENC_SHAPES = {
     "pieces": ((("toy49", 8), ("toy60", 16)), dict(pieces=3, tail=0, nt=False, second_round=False, per_access=True)),
     "pieces+tail": ((("toy49", 7), ("toy60", 14)), dict(pieces=2, tail=1280, nt=False, second_round=False, per_access=True)),
     "nt+round2": ((("C2", 70),), dict(pieces=2240, tail=0, nt=True, second_round=True, per_access=False)),
-    "nt+round2+tail": ((("mid", 1501), ("mid60", 1501)), dict(pieces=2251, tail=1024, nt=True, second_round=True, per_access=True)),
+    "nt+round2+tail": ((("mid", 1501), ("mid50", 1501), ("mid60", 1501)), dict(pieces=2251, tail=1024, nt=True, second_round=True, per_access=True)),
 }
 IN_PLACE = ("pieces+tail", "nt+round2+tail")
 RING_OPS = ("add", "sub", "mul", "neg", "add_scalar", "mul_scalar")

@@ -69,9 +69,9 @@ def assert_switch_matches_mirror(dev, prm, enc, K_in, K_out):
     assert (got == want).all(), (prm.name, K_in, K_out, np.argwhere(got != want)[:4])
 
 
-@pytest.mark.parametrize("name", ["toy", "toy49", "toy54", "toy60"])
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "toy54", "toy60"])
 def test_mod_switch_is_the_mirror_word_for_word(name):
-    """toy, toy49: the FP64 arithmetic; toy54, toy60: the integer one.  Every (K_in, K_out), count 1 and 5."""
+    """toy, toy49, toy50: the FP64 arithmetic; toy54, toy60: the integer one.  Every (K_in, K_out), count 1 and 5."""
     prm = P.preset(name)
     dev = device_for(name)
     assert (name in ("toy54", "toy60")) == any(p >= 1 << 50 for p in prm.q + prm.Q)

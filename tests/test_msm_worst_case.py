@@ -135,6 +135,31 @@ CASES = [
     # 6: hybrid context: 54-bit ring prime on the integer arithmetic, FP64 multiply-accumulate of the 48 / 49-bit data primes
     ("hybrid8192", "poly", 1, 1, {}, ("mac_kernel_v3", PLAIN), False),
     ("hybrid8192", "poly", 2, 2, {}, ("mac_kernel_v4<13, false>", PLAIN), False),
+    # 7: the rows of 1-4 and 6 on primes just below 2^50, the largest the FP64 arithmetic accepts: the accumulator period is
+    # 4 terms, the shortest there is, and four products of up to 0.875 p each leave reduce() no room beyond 2^52 = 4 p
+    ("toy50", "poly", 1, 1, {}, ("mac_kernel",), True),
+    ("toy50", "poly", 2, 1, {}, ("mac_kernel",), True),
+    ("toy50", "poly", 1, 2, {}, ("mac_kernel",), True),
+    ("toy50", "one", 2, 1, {}, ("mac_kernel",), False),
+    ("toy50", "const", 1, 2, {}, ("mac_kernel",), False),
+    ("n2048q50", "poly", 1, 1, {}, ("mac_kernel_v2",), True),
+    ("n2048q50", "poly", 1, 1, dict(mac_variant=1), ("mac_kernel",), True),
+    ("n2048q50", "one", 1, 1, {}, ("mac_kernel_v2",), False),
+    ("n2048q50", "const", 1, 1, {}, ("mac_kernel_v2",), False),
+    ("n8192q50", "poly", 1, 1, {}, ("mac_kernel_v3", WIDE), True),
+    ("n8192q50", "poly", 2, 1, dict(plain_variant=0), ("mac_kernel_v3", PLAIN), True),
+    ("n8192q50", "poly", 1, 1, dict(mac_variant=3), ("mac_kernel_v2", WIDE), True),
+    ("n8192q50", "poly", 1, 2, {}, ("mac_kernel_v4<13, true>", WIDE), True),
+    ("n8192q50", "poly", 2, 2, dict(plain_variant=0), ("mac_kernel_v4<13, false>", PLAIN), True),
+    ("n8192q50", "one", 1, 1, {}, ("mac_kernel_v3", WIDE), False),
+    ("n8192q50", "const", 1, 1, {}, ("mac_kernel_v3", WIDE), False),
+    ("n8192q50", "one", 1, 2, {}, ("mac_kernel_v4<13, true>", WIDE), False),
+    ("n8192q50", "const", 1, 2, dict(plain_variant=0), ("mac_kernel_v4<13, false>", PLAIN), False),
+    ("n16384q50", "poly", 1, 1, {}, ("mac_kernel_v3<false, 14>",), False),
+    ("n16384q50", "poly", 1, 2, {}, ("mac_kernel_v4<14, false>",), False),
+    ("n16384q50", "poly", 1, 1, dict(mac_variant=1), ("mac_kernel",), False),
+    ("hybrid8192q50", "poly", 1, 1, {}, ("mac_kernel_v3", PLAIN), False),
+    ("hybrid8192q50", "poly", 2, 2, {}, ("mac_kernel_v4<13, false>", PLAIN), False),
 ]
 
 
@@ -144,7 +169,8 @@ def test_aligned_sums_equal_the_closed_form(name, variant, n_groups, n_keys, kno
     check_case(name, variant, n_groups, n_keys, knobs, kernels, oracle)
 
 
-EXTREME_KERNEL = {"n8192": "mac_kernel_v3", "hybrid8192": "mac_kernel_v3", "n16384full": "mac_kernel_v3<false, 14>"}
+EXTREME_KERNEL = {"n8192": "mac_kernel_v3", "hybrid8192": "mac_kernel_v3", "n16384full": "mac_kernel_v3<false, 14>",
+                  "n8192q50": "mac_kernel_v3"}
 
 
 @pytest.mark.parametrize("name", sorted(H.EXTREME_CASES))

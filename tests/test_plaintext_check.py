@@ -109,7 +109,7 @@ def reference_flow(name, constants):
     return dict(prm=prm, ctx=ctx, cs=cs, asg=asg, vk=vk, proof=proof, empty=empty)
 
 
-@pytest.mark.parametrize("name", ["toy", "toy49", "toy60"])
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "toy60"])
 def test_the_form_without_constants_passes_the_reference_flow(name):
     c = reference_flow(name, False)
     ctx, vk, cs = c["ctx"], c["vk"], c["cs"]
@@ -160,7 +160,7 @@ def uploaded(dev, cs, xs):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("scheme,name", [("rinocchio", "toy"), ("groth16", "toy"), ("rinocchio", "toy60")])
+@pytest.mark.parametrize("scheme,name", [("rinocchio", "toy"), ("groth16", "toy"), ("rinocchio", "toy50"), ("rinocchio", "toy60")])
 def test_device_pipeline_on_device_made_bits(scheme, name):
     from ringsnark_amd.device import Device, to_host
     c = device_case(scheme, name)

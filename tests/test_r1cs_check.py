@@ -268,7 +268,7 @@ def test_device_check_matches_reference_headers_fixture_poly(force_int):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("m", [1, 33, 1000])
-@pytest.mark.parametrize("preset", ["toy", "toy49", "toy54", "toy60"])
+@pytest.mark.parametrize("preset", ["toy", "toy49", "toy50", "toy54", "toy60"])
 def test_device_check_both_arithmetics(preset, m):
     from ringsnark_amd.device import Device
     prm, cs, asg = system(preset, "wide", m)
@@ -294,6 +294,24 @@ def test_device_check_long_rows_at_the_fp64_corner():
     """rows of 68 terms on 49-bit primes: the lazy sums must be reduced every four terms (f64mod.hpp)"""
     from ringsnark_amd.device import Device
     prm, cs, asg = system("toy49", "wide", 40, 67)
+    dev = Device(prm)
+    dcs = dev.r1cs(cs)
+    exp = expected_report(prm, cs, asg)
+    assert exp.satisfied
+    assert_same(device_report(dev, dcs, asg), exp)
+    bad = tampered(prm, asg, (3, 1, 17))
+    exp = expected_report(prm, cs, bad)
+    assert 1 <= exp.n_violated < 40
+    assert_same(device_report(dev, dcs, bad), exp)
+
+
+@pytest.mark.gpu
+def test_device_check_long_rows_at_the_top_of_the_fp64_range():
+    """the same rows of 68 terms on primes just below 2^50: four products of up to 0.875 p each (f64mod.hpp's second regime)
+    reach 3.5 p of the 4 p = 2^52 a reduction accepts"""
+    from ringsnark_amd.device import Device
+    prm, cs, asg = system("toy50", "wide", 40, 67)
+    assert all(1 << 49 < p < 1 << 50 for p in prm.q)
     dev = Device(prm)
     dcs = dev.r1cs(cs)
     exp = expected_report(prm, cs, asg)

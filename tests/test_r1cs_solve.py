@@ -83,10 +83,12 @@ def mixed_r1cs(W, q):
 
 @functools.lru_cache(maxsize=None)
 def system(name):
+    """"<system>@<preset>": the system on that preset's ring instead of toy's"""
+    name, _, preset = name.partition("@")
     if name in ("ring256_wide40", "mixed"):
         prm = ring256()
     else:
-        prm = P.preset("toy")
+        prm = P.preset(preset or "toy")
     if name == "mixed":
         chunks = -(-(prm.L * prm.N // 2) // 256)
         W = -(-R.SOLVE_FILL_WORKGROUPS // chunks)  # the smallest width that RS_SOLVE_AUTO gives to the level kernel on this ring
@@ -290,6 +292,26 @@ def test_device_solve_every_mode_both_arithmetics(name, force_int):
             assert (got == exp).all(), (mode, np.argwhere(got != exp)[:4])
             assert dev.r1cs_check(dcs, dasg).n_violated == 0
             assert_stats(stats, mode, plan.info)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["wide40@toy49", "wide40@toy50", "poly20@toy50"])
+def test_device_solve_at_the_top_of_the_fp64_range(name):
+    """49-bit primes and primes just below 2^50 (toy50: the largest the FP64 arithmetic accepts, N = 64): every product of
+    two loaded wires is canonical x canonical, up to p^2 (f64mod.hpp's second regime).  Every mode against R.solve."""
+    from ringsnark_amd.device import Device
+    prm, cs, given, asg = system(name)
+    assert all(p < 1 << 50 for p in prm.q + prm.Q) and (name.endswith("toy50")) == all(p > 1 << 49 for p in prm.q)
+    exp = solved(name)
+    dev = Device(prm)
+    dcs = dev.r1cs(cs)
+    plan = dev.r1cs_solve_plan(dcs, given)
+    assert plan.info.n_unsolved == 0
+    for mode in MODES:
+        got, stats, dasg = run_device(dev, dcs, plan, asg, mode)
+        assert (got == exp).all(), (mode, np.argwhere(got != exp)[:4])
+        assert dev.r1cs_check(dcs, dasg).n_violated == 0
+        assert_stats(stats, mode, plan.info)
 
 
 @pytest.mark.gpu

@@ -101,7 +101,7 @@ def test_oracle_scalar_one_decrypts_like_the_polynomial_wire():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["toy", "toy49", "toy60", "C2"])
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "toy60", "C2"])
 def test_device_provers_honour_scalar_one_wires(name):
     from ringsnark_amd.device import Device, to_host
     prm = P.preset(name)

@@ -148,7 +148,7 @@ def seeded_case(dev, scheme, name, cs, host=False, tile=0, seeds=700, pub=PUB, s
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,count", [("toy", 5), ("toy49", 5), ("toy60", 5), ("C2", 3), ("C5s", 2)])
+@pytest.mark.parametrize("name,count", [("toy", 5), ("toy49", 5), ("toy50", 5), ("toy60", 5), ("C2", 3), ("C5s", 2)])
 def test_expansion_equals_the_encoder(name, count):
     """c0 of rs_enc_encode's elements and the same seed give the elements back: c1 is the encoder's stream, % Q_j by the
     Barrett form (toy60: 60-bit Q_j on the integer arithmetic).  C2: N_enc = 8192, K = 4 (four workgroups per row); C5s:
@@ -171,7 +171,7 @@ def test_expansion_equals_the_encoder(name, count):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("scheme", ["groth16", "rinocchio"])
-@pytest.mark.parametrize("name", ["toy", "toy49", "toy60"])
+@pytest.mark.parametrize("name", ["toy", "toy49", "toy50", "toy60"])
 def test_seeded_keygen_is_c0_of_the_full_key_when_the_seeds_coincide(name, scheme):
     from ringsnark_amd.device import to_host
     prm = P.preset(name)
@@ -267,6 +267,7 @@ def proof_case(name, scheme, m, zk):
 
 
 PROOF_CASES = [("toy", "groth16", False), ("toy", "rinocchio", True), ("toy49", "groth16", False), ("toy49", "rinocchio", False),
+               ("toy50", "groth16", False), ("toy50", "rinocchio", False),
                ("toy60", "groth16", False), ("toy60", "rinocchio", False)]
 
 

@@ -10,7 +10,7 @@ keys from snark_ref's generators, the oracle's prover, positive noise budget eve
 Rinocchio with the ZK elements d1..d3 set multiplies every term of <s_pows, .> by TWO plaintexts (the coefficient of Z and
 d_i, rinocchio.tcc:150-160): on `toy49` (and the integer presets `toy54`, `toy60`) that spends the whole budget of V..Y' --
 the reference's verifier throws on such a proof -- so the ZK case runs on `toy`, whose 30-bit plain moduli leave 26 bits,
-and `toy49` / `toy60` run without ZK elements."""
+and `toy49` / `toy50` / `toy60` run without ZK elements."""
 import functools
 import os
 import re
@@ -27,8 +27,8 @@ from tests import snark_ref as S
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE = 64  # rows per tile of rs_io_eval_at (ringsnark_amd.device.IO_EVAL_TILE)
 
-G16_CASES = [("toy", 6), ("toy49", 12), ("toy60", 6)]  # toy60: the integer (Montgomery) arithmetic
-RIN_CASES = [("toy49", 9, False), ("toy", 9, True), ("toy60", 9, False)]  # (preset, m, ZK elements set)
+G16_CASES = [("toy", 6), ("toy49", 12), ("toy50", 12), ("toy60", 6)]  # toy60: the integer (Montgomery) arithmetic
+RIN_CASES = [("toy49", 9, False), ("toy50", 9, False), ("toy", 9, True), ("toy60", 9, False)]  # (preset, m, ZK elements set)
 
 
 # ---- shared inputs (CPU, computed once) ------------------------------------------------------------------------------
@@ -233,7 +233,7 @@ def assert_io_eval_matches_instance_map(dev, cs, s):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,force_int", [("toy", 0), ("toy49", 0), ("toy60", 0), ("toy", 1)])
+@pytest.mark.parametrize("name,force_int", [("toy", 0), ("toy49", 0), ("toy50", 0), ("toy60", 0), ("toy", 1)])
 def test_io_eval_at_matches_instance_map_eval(name, force_int):
     """Rows 0..n_inputs of At / Bt / Ct and Zt, bit for bit, on both arithmetics: m around the tile, several tiles with a
     ragged last one (more than one workgroup per slot chunk), an empty row, polynomial coefficients on public columns,
