@@ -242,6 +242,16 @@ BITS_SIGNATURES = {  # every function of include/ringsnark_amd/bits.h
     "rs_ring_bit_decompose": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(BitsReport), vp]),
 }
 
+VERIFY_BATCH_SIGNATURES = {  # every function of include/ringsnark_amd/verify_batch.h
+    "rs_verify_batch_group": (C.c_int, []),
+    "rs_groth16_verify_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                          C.POINTER(VerifyReport), vp]),
+    "rs_rinocchio_verify_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.POINTER(VerifyReport), vp]),
+}
+VERIFY_BATCH_MAX = 64  # RS_VERIFY_BATCH_MAX
+VERIFY_BATCH_GROUP = 4  # rs_verify_batch_group(): proofs whose public sums one thread of the check kernel carries (csrc/verify.hip VERIFY_PB)
+
 _lib = None
 
 
@@ -256,7 +266,8 @@ def load():
             "the HIP library is the only implementation, there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **SOLVE_SIGNATURES, **VERIFY_SIGNATURES,
-                              **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES, **MODSWITCH_SIGNATURES, **BITS_SIGNATURES}.items():
+                              **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES, **MODSWITCH_SIGNATURES, **BITS_SIGNATURES,
+                              **VERIFY_BATCH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -269,7 +269,8 @@ using namespace rs;
 // rs::decode_impl (declared in rs_internal.hpp, defined below; modswitch.hip and verify.hip call it too):
 // EncodingElem::decode and Decryptor::invariant_noise_budget share everything up to the centred composition.
 // d_rings == nullptr: budgets only.  h_budget [count * L] (may be null).  Throws RS_ERR_NOISE -- after writing every
-// decoding -- when d_rings is given and a ciphertext has no budget left (seal_ring.tcc:446-454).
+// decoding -- when d_rings is given and a ciphertext has no budget left (seal_ring.tcc:446-454).  rs::decode_held is the same
+// body for a caller that holds the context's lock and reads the verdict from h_budget instead (verify.hip, a batch of proofs).
 // K: the level -- the first K primes of the context, d_enc [count][L][2][K][N_enc]; below ctx->K the decoding is
 // multiplied by the level factor (modswitch.h).
 extern "C" {
@@ -368,7 +369,7 @@ static std::vector<CrtLimbT<M>> crt_limbs(const rs_ctx *ctx, int K) {
 // decode_impl in the arithmetic M; the caller holds the context's WsScope
 template <class M>
 static int decode_arith(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
-                        hipStream_t st) {
+                        bool guard, hipStream_t st) {
   using T = typename ArithOf<M>::T;
   constexpr bool FP = std::is_same<M, Mod>::value;
   const int L = ctx->L, n = ctx->N_enc, logn = ctx->logN_enc;
@@ -410,7 +411,7 @@ static int decode_arith(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t
   }
   RS_HIP(hipGetLastError());
   RS_HIP(hipStreamSynchronize(st));
-  return noise_verdict(ctx, d_bits, count, tb, d_rings != nullptr, h_budget);
+  return noise_verdict(ctx, d_bits, count, tb, guard, h_budget);
 }
 
 int rs::decode_impl(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
@@ -418,8 +419,21 @@ int rs::decode_impl(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_
   if (count == 0) return RS_OK;
   WsScope ws_scope(ctx, S(stream));  // holds ctx->mu: the lazily built constants are built once
   int rc = RS_OK;
-  dispatch_arith(ctx, [&](auto tag) { rc = decode_arith<decltype(tag)>(ctx, K, d_sk, d_enc, count, d_rings, h_budget, S(stream)); });
+  dispatch_arith(ctx, [&](auto tag) { rc = decode_arith<decltype(tag)>(ctx, K, d_sk, d_enc, count, d_rings, h_budget, d_rings != nullptr, S(stream)); });
   return rc;
+}
+
+void rs::decode_held(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
+                     hipStream_t st) {
+  if (count == 0) return;
+  dispatch_arith(ctx, [&](auto tag) { decode_arith<decltype(tag)>(ctx, K, d_sk, d_enc, count, d_rings, h_budget, false, st); });
+}
+
+int rs::level_bit_count(const rs_ctx *ctx, int K) {
+  BigU Q;
+  Q.w[0] = 1;
+  for (int k = 0; k < K; k++) Q.mul_add(ctx->Q[k], 0);
+  return Q.bits();
 }
 
 extern "C" {

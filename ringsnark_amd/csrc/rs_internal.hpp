@@ -162,6 +162,8 @@ enum WsSlot {
   WS_KEYGEN_STAGE,   // keygen_run (keygen.hip) with a host-resident key: the two staging buffers of encoded tiles, [2][tile] encoding elements (ciphertexts only, nothing secret)
   WS_MODSWITCH_LEVELS,  // mod_switch_run (modswitch.hip): the intermediate levels of a switch of more than one step, two buffers used in turn,
                      // [count][L][2][K_in - 1][N_enc] and [count][L][2][K_in - 2][N_enc]
+  WS_VERIFY_BATCH,   // verify_batch (verify.hip): the decoded elements of every proof of the batch, [batch][3 | 9][L][N], then the report words [batch][VERIFY_WORDS].
+                     // Taken once, before the decodes of the same scope (decode_held takes WS_NOISE_BITS and WS_STAGE_ROWS only).
   WS_COUNT
 };
 
@@ -398,6 +400,12 @@ void instance_map_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uint6
 // only.  Takes the context's WsScope itself; returns RS_OK or throws (RS_ERR_NOISE: the guard).
 int decode_impl(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
                 rs_stream stream);
+// encoding.hip.  decode_impl for a caller that HOLDS the context's WsScope and wants the noise verdict as data: d_rings and
+// h_budget [count * L] are both written and a spent budget does not throw (verify.hip: a batch of proofs, one verdict each).
+void decode_held(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
+                 hipStream_t st);
+// encoding.hip.  bit_count(Q[0] * .. * Q[K - 1]): rs_enc_noise_budget_level of a ciphertext whose noise polynomial is zero is this - 1
+int level_bit_count(const rs_ctx *ctx, int K);
 // encoding.hip.  The wire format at level K.  deserialize_run: K_want == 0 accepts every level 1..ctx->K and reports it.
 size_t wire_size(const rs_ctx *ctx, int K, size_t count);
 void serialize_run(rs_ctx *ctx, int K, const uint64_t *d_enc, const uint8_t *h_empty, size_t count, void *h_buf, size_t buf_bytes,

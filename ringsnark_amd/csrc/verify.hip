@@ -19,9 +19,11 @@
 #include <algorithm>
 #include <cstring>
 #include <mutex>
+#include <utility>
 
 #include "../../include/ringsnark_amd/modswitch.h"
 #include "../../include/ringsnark_amd/verify.h"
+#include "../../include/ringsnark_amd/verify_batch.h"
 #include "witness_eval.hpp"
 
 namespace rs {
@@ -296,22 +298,32 @@ __device__ __forceinline__ typename ArithOf<M>::T mul_cc(typename ArithOf<M>::T 
   return mulmod_dd(center(a, mod), b, mod);
 }
 
-// The checks of one slot: canonical residues lhs[c], rhs[c] of check c (verify.h).  SCHEME 0: groth16 (1 check), 1: rinocchio (6).
-template <class M, int SCHEME>
-__device__ __forceinline__ void verify_slot(const VerifyArgs &a, size_t S, size_t i, const M &mod, uint64_t (&lhs)[6], uint64_t (&rhs)[6]) {
+// A verification of one slot is two parts: the public sums v_io(s), w_io(s), y_io(s) = column 0 + sum_k x_k * column k
+// (canonical residues), and the checks given those sums and the decoded proof elements.  The batch kernel computes the sums
+// of several proofs side by side (verify_batch_kernel) and shares the checks.
+template <class M>
+__device__ __forceinline__ void io_sums(const VerifyArgs &a, const uint64_t *__restrict__ primary, size_t S, size_t i, const M &mod,
+                                        typename ArithOf<M>::T (&io)[3]) {
   using T = typename ArithOf<M>::T;
   auto ld = [&](const uint64_t *p) { return from_res<T>(p[i]); };
-  // v_io(s), w_io(s), y_io(s) = column 0 + sum_k x_k * column k
-  T io[3];
 #pragma unroll
   for (int w = 0; w < 3; w++) {
     T acc = ld(a.io[w]);
     for (unsigned k = 0; k < a.n_inputs; k++)
-      acc = reduce(addm(acc, mul_cc<M>(ld(a.primary + (size_t)k * S), ld(a.io[w] + (size_t)(k + 1) * S), mod), mod), mod);
+      acc = reduce(addm(acc, mul_cc<M>(ld(primary + (size_t)k * S), ld(a.io[w] + (size_t)(k + 1) * S), mod), mod), mod);
     io[w] = canon(acc, mod);
   }
+}
+
+// The checks of one slot: canonical residues lhs[c], rhs[c] of check c (verify.h).  SCHEME 0: groth16 (1 check), 1: rinocchio (6).
+// dec: [3 | 9][S] decoded elements of the proof, io: its public sums at this slot.
+template <class M, int SCHEME>
+__device__ __forceinline__ void verify_checks(const VerifyArgs &a, const uint64_t *__restrict__ dec, size_t S, size_t i, const M &mod,
+                                              const typename ArithOf<M>::T (&io)[3], uint64_t (&lhs)[6], uint64_t (&rhs)[6]) {
+  using T = typename ArithOf<M>::T;
+  auto ld = [&](const uint64_t *p) { return from_res<T>(p[i]); };
   if (SCHEME == 0) {
-    const T A = ld(a.dec), B = ld(a.dec + S), C = ld(a.dec + 2 * S);
+    const T A = ld(dec), B = ld(dec + S), C = ld(dec + 2 * S);
     const T alpha = ld(a.el[0]), beta = ld(a.el[1]), delta = ld(a.el[2]);
     // f = beta v_io + alpha w_io + y_io  (= gamma * (f / gamma): groth16.tcc:159-166 for an invertible gamma)
     const T f = reduce(addm(reduce(addm(mul_cc<M>(beta, io[0], mod), mul_cc<M>(alpha, io[1], mod), mod), mod), io[2], mod), mod);
@@ -322,7 +334,7 @@ __device__ __forceinline__ void verify_slot(const VerifyArgs &a, size_t S, size_
     const T alpha = ld(a.el[0]), beta = ld(a.el[1]);
     T x[9];
 #pragma unroll
-    for (int e = 0; e < 9; e++) x[e] = ld(a.dec + (size_t)e * S);
+    for (int e = 0; e < 9; e++) x[e] = ld(dec + (size_t)e * S);
 #pragma unroll
     for (int c = 0; c < 4; c++) {  // V', W', Y', H' against alpha * V, W, Y, H
       lhs[c] = to_res(x[2 * c + 1]);
@@ -336,6 +348,14 @@ __device__ __forceinline__ void verify_slot(const VerifyArgs &a, size_t S, size_
     lhs[5] = to_res(canon(subm(mul_cc<M>(pv, pw, mod), py, mod), mod));
     rhs[5] = to_res(canon(mul_cc<M>(x[6], ld(a.Zt), mod), mod));
   }
+}
+
+// both parts for the proof that `a` names (a.primary, a.dec)
+template <class M, int SCHEME>
+__device__ __forceinline__ void verify_slot(const VerifyArgs &a, size_t S, size_t i, const M &mod, uint64_t (&lhs)[6], uint64_t (&rhs)[6]) {
+  typename ArithOf<M>::T io[3];
+  io_sums<M>(a, a.primary, S, i, mod, io);
+  verify_checks<M, SCHEME>(a, a.dec, S, i, mod, io, lhs, rhs);
 }
 
 // A thread owns a slot pair.  An accepted proof issues no atomic.
@@ -391,6 +411,151 @@ static void verify_run(rs_ctx *ctx, const VerifyArgs &a, unsigned long long *rep
   }
   RS_HIP(hipGetLastError());
   hipLaunchKernelGGL((verify_finish_kernel<M, SCHEME>), dim3(1), dim3(64), 0, st, a, ctx->N, S, CtxArith<M>::qmod(ctx), rep);
+  RS_HIP(hipGetLastError());
+}
+
+// ---- a batch of proofs against one key (verify_batch.h) ---------------------------------------------------------------
+// Proofs whose public sums a thread carries at once.  A column of the key is read once per VERIFY_PB proofs: per proof
+// (3 (n_inputs + 1) / VERIFY_PB + n_inputs) S words instead of (4 n_inputs + 3) S.  The accumulators are VERIFY_PB x 3 sums x
+// 2 slots 64-bit words (48 VGPRs at 4); the checks that follow, with the other proofs' sums still live, set the kernel's
+// count: 92..136 VGPRs and 3 to 5 waves per SIMD at 4, 162..184 and 2 to 3 at 8, no scratch either way.  4, not 8, by
+// measurement (profiles/verify_batch.txt): a wave does the modular products of VERIFY_PB proofs one after the other, and at
+// the logistic-regression shape (1024 slot pairs, 517 inputs, integer arithmetic) a batch of 64 is 16 waves x 64 / VERIFY_PB
+// groups -- the kernel is bound by the products of one wave, not by the columns, and took 5.5 ms at 8 against 2.8 ms at 4;
+// at the headline shape both take the same time.
+constexpr int VERIFY_PB = 4;
+
+// f(integral_constant<int, P>) for every P of the sequence: indices into a register array that are constants by construction
+template <int... P, class F>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, P...>, F &&f) {
+  (f(std::integral_constant<int, P>{}), ...);
+}
+
+// the two words of a slot pair, one 16-byte load where the array is 16-byte aligned (S and the pair's first index are even)
+__device__ __forceinline__ void ld_pair(const uint64_t *__restrict__ p, bool vec, uint64_t (&v)[2]) {
+  if (vec) {
+    const ulonglong2 t = *reinterpret_cast<const ulonglong2 *>(p);
+    v[0] = t.x, v[1] = t.y;
+  } else {
+    v[0] = p[0], v[1] = p[1];
+  }
+}
+
+// a.primary [batch][n_inputs][S], a.dec [batch][3 | 9][S]; rep [batch][VERIFY_WORDS], zero before the launch, word 0 of a
+// proof: the COMPLEMENT of the key of its first failure (zero: none; one memset prepares every word), the others as in the
+// single kernel.  grid (chunks of 256 slot pairs, groups of VERIFY_PB proofs).  As in verify_kernel a thread owns a slot pair
+// and the lanes of a wave hold ascending pairs.  skip4 bit b: check 4 is not made for proof b.  The tail group's guard
+// p < nb is wave-uniform.
+template <class M, int SCHEME>
+__global__ void __launch_bounds__(256)
+verify_batch_kernel(VerifyArgs a, int batch, unsigned long long skip4, int prim_vec, int N, size_t S, const M *__restrict__ qmod,
+                    unsigned long long *__restrict__ rep) {
+  using T = typename ArithOf<M>::T;
+  constexpr int NE = SCHEME == 0 ? 3 : 9, NC = SCHEME == 0 ? 1 : 6;
+  const size_t pair = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = 2 * pair < S;
+  const size_t i = live ? 2 * pair : 0;
+  const int b0 = (int)blockIdx.y * VERIFY_PB;
+  const int nb = batch - b0 < VERIFY_PB ? batch - b0 : VERIFY_PB;
+  const M mod = qmod[i / (size_t)N];
+  T acc[VERIFY_PB][3][2];
+  if (live) {
+    uint64_t c[2];
+#pragma unroll
+    for (int w = 0; w < 3; w++) {
+      ld_pair(a.io[w] + i, true, c);
+#pragma unroll
+      for (int p = 0; p < VERIFY_PB; p++) acc[p][w][0] = from_res<T>(c[0]), acc[p][w][1] = from_res<T>(c[1]);
+    }
+    const size_t pstride = (size_t)a.n_inputs * S;
+    for (unsigned k = 0; k < a.n_inputs; k++) {
+      T col[3][2];  // column k + 1 of the three matrices: loaded once, used by every proof of the group
+#pragma unroll
+      for (int w = 0; w < 3; w++) {
+        ld_pair(a.io[w] + (size_t)(k + 1) * S + i, true, c);
+        col[w][0] = from_res<T>(c[0]), col[w][1] = from_res<T>(c[1]);
+      }
+      const uint64_t *xk = a.primary + (size_t)b0 * pstride + (size_t)k * S + i;
+#pragma unroll
+      for (int p = 0; p < VERIFY_PB; p++) {
+        if (p < nb) {
+          ld_pair(xk + (size_t)p * pstride, prim_vec != 0, c);
+#pragma unroll
+          for (int h = 0; h < 2; h++) {
+            const T x = center(from_res<T>(c[h]), mod);
+#pragma unroll
+            for (int w = 0; w < 3; w++) acc[p][w][h] = reduce(addm(acc[p][w][h], mulmod_dd(x, col[w][h], mod), mod), mod);
+          }
+        }
+      }
+    }
+  }
+  static_for(std::make_integer_sequence<int, VERIFY_PB>{}, [&](auto pc) {
+    constexpr int p = decltype(pc)::value;
+    if (p < nb) {
+      unsigned bad[2] = {0u, 0u};
+      if (live) {
+        const uint64_t *dec = a.dec + (size_t)(b0 + p) * NE * S;
+        const unsigned skip = (SCHEME == 1 && ((skip4 >> (b0 + p)) & 1ull)) ? 1u << 4 : 0u;
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const T io[3] = {canon(acc[p][0][h], mod), canon(acc[p][1][h], mod), canon(acc[p][2][h], mod)};
+          uint64_t lhs[6], rhs[6];
+          verify_checks<M, SCHEME>(a, dec, S, i + h, mod, io, lhs, rhs);
+#pragma unroll
+          for (int c = 0; c < NC; c++)
+            if (lhs[c] != rhs[c] && !((skip >> c) & 1u)) bad[h] |= 1u << c;
+        }
+      }
+      unsigned long long *rp = rep + (size_t)(b0 + p) * VERIFY_WORDS;
+#pragma unroll
+      for (int c = 0; c < NC; c++) {
+        const bool f0 = (bad[0] >> c) & 1u, f1 = (bad[1] >> c) & 1u;
+        const unsigned long long v0 = __ballot(f0), v1 = __ballot(f1);
+        if ((v0 | v1) == 0ull) continue;  // wave-uniform: an accepted proof issues no atomic
+        if ((int)(threadIdx.x & 63u) == __ffsll((long long)(v0 | v1)) - 1) {
+          atomicAdd(rp + 1 + c, (unsigned long long)(__popcll(v0) + __popcll(v1)));
+          atomicMax(rp, ~(unsigned long long)((size_t)c * S + 2 * pair + (f0 ? 0 : 1)));  // the smallest key has the largest complement
+        }
+      }
+    }
+  });
+}
+
+// the two residues at the first failure of every proof: one wave per proof
+template <class M, int SCHEME>
+__global__ void __launch_bounds__(64)
+verify_batch_finish_kernel(VerifyArgs a, int N, size_t S, const M *__restrict__ qmod, unsigned long long *__restrict__ rep) {
+  constexpr int NE = SCHEME == 0 ? 3 : 9;
+  unsigned long long *rp = rep + (size_t)blockIdx.x * VERIFY_WORDS;
+  const unsigned long long inv = rp[0];  // final: written by the launch before this one
+  if (threadIdx.x != 0 || inv == 0ull) return;
+  const unsigned long long key = ~inv;
+  const size_t c = (size_t)(key / S), i = (size_t)(key % S);
+  if (a.n_inputs) a.primary += (size_t)blockIdx.x * a.n_inputs * S;
+  a.dec += (size_t)blockIdx.x * NE * S;
+  uint64_t lhs[6] = {0, 0, 0, 0, 0, 0}, rhs[6] = {0, 0, 0, 0, 0, 0};
+  verify_slot<M, SCHEME>(a, S, i, qmod[i / (size_t)N], lhs, rhs);
+  rp[7] = lhs[c];
+  rp[8] = rhs[c];
+}
+
+template <class M, int SCHEME>
+static void verify_batch_run(rs_ctx *ctx, const VerifyArgs &a, int batch, unsigned long long skip4, unsigned long long *rep, hipStream_t st) {
+  constexpr int NE = SCHEME == 0 ? 3 : 9, NEL = SCHEME == 0 ? 3 : 6;
+  const size_t S = ctx->ring_words();
+  const int groups = (batch + VERIFY_PB - 1) / VERIFY_PB;
+  const int prim_vec = (reinterpret_cast<uintptr_t>(a.primary) & 15u) == 0 ? 1 : 0;
+  {
+    // algorithmic bytes: the columns and the key's elements once per group, its own inputs and decodings once per proof
+    ProfScope p(ctx, st, SCHEME == 0 ? "groth16_verify" : "rinocchio_verify",
+                (groups * (3.0 * (a.n_inputs + 1) + NEL) + (double)batch * (a.n_inputs + NE)) * S * 8,
+                7.0 * (3.0 * a.n_inputs + (SCHEME == 0 ? 5 : 10)) * S * batch);
+    hipLaunchKernelGGL((verify_batch_kernel<M, SCHEME>), dim3((unsigned)((S / 2 + 255) / 256), (unsigned)groups), dim3(256), 0, st, a, batch,
+                       skip4, prim_vec, ctx->N, S, CtxArith<M>::qmod(ctx), rep);
+  }
+  RS_HIP(hipGetLastError());
+  hipLaunchKernelGGL((verify_batch_finish_kernel<M, SCHEME>), dim3((unsigned)batch), dim3(64), 0, st, a, ctx->N, S, CtxArith<M>::qmod(ctx), rep);
   RS_HIP(hipGetLastError());
 }
 
@@ -480,6 +645,26 @@ static void vk_create(rs_ctx *ctx, int scheme, const rs_r1cs *cs, const uint64_t
   *out = reinterpret_cast<VK *>(vk);
 }
 
+// the report from the downloaded words h [VERIFY_WORDS] of one proof; key: (check * S + position) of its first failure
+static rs_verify_report report_of(const rs_ctx *ctx, const unsigned long long *h, int NC, bool has_first, unsigned long long key) {
+  const size_t S = ctx->ring_words();
+  rs_verify_report out{};
+  for (int c = 0; c < NC; c++) {
+    out.n_bad[c] = h[1 + c];
+    if (h[1 + c]) out.failed |= 1u << c;
+  }
+  out.accepted = out.failed == 0 ? 1u : 0u;
+  if (has_first) {
+    const size_t idx = (size_t)(key % S);
+    out.first_check = (uint32_t)(key / S);
+    out.first_limb = (uint32_t)(idx / (size_t)ctx->N);
+    out.first_slot = (uint32_t)(idx % (size_t)ctx->N);
+    out.lhs = h[7];
+    out.rhs = h[8];
+  }
+  return out;
+}
+
 // K_lvl: the level of the proof, d_proof [NE][L][2][K_lvl][N_enc] (ctx->K: an unswitched proof; modswitch.h)
 template <int SCHEME>
 static void verify(rs_ctx *ctx, int K_lvl, const VkBase *cvk, const uint64_t *d_primary, const uint64_t *d_proof, const int *h_empty,
@@ -525,21 +710,71 @@ static void verify(rs_ctx *ctx, int K_lvl, const VkBase *cvk, const uint64_t *d_
     RS_HIP(hipMemcpyAsync(h, vk->rep, sizeof(h), hipMemcpyDeviceToHost, st));
     RS_HIP(hipStreamSynchronize(st));
   }
-  rs_verify_report out{};
-  for (int c = 0; c < NC; c++) {
-    out.n_bad[c] = h[1 + c];
-    if (h[1 + c]) out.failed |= 1u << c;
+  *h_report = report_of(ctx, h, NC, h[0] != ~0ull, h[0]);
+}
+
+// verify_batch.h.  The decodings and the report words of the whole batch live in the context's workspace, under the
+// context's lock from the first decode to the download: the key is only read.
+template <int SCHEME>
+static void verify_batch(rs_ctx *ctx, const VkBase *vk, int K_lvl, int batch, const uint64_t *d_primary, const uint64_t *d_proofs,
+                         const int *h_empty, int *h_status, int *h_budget_min, rs_verify_report *h_reports, hipStream_t st) {
+  constexpr int NE = SCHEME == 0 ? 3 : 9, NC = SCHEME == 0 ? 1 : 6;
+  RS_REQUIRE(K_lvl >= 1 && K_lvl <= ctx->K, "level out of range: 1 <= K_lvl <= K");
+  RS_REQUIRE(vk != nullptr, "null argument");
+  RS_REQUIRE(vk->ctx == ctx, "verification key of another context");
+  RS_REQUIRE(vk->scheme == SCHEME, "verification key of the other scheme");
+  RS_REQUIRE(batch >= 0 && batch <= RS_VERIFY_BATCH_MAX, "batch out of range: 0 <= batch <= RS_VERIFY_BATCH_MAX");
+  if (batch == 0) return;
+  RS_REQUIRE(d_proofs && h_status && h_reports, "null argument");
+  RS_REQUIRE(d_primary || vk->n_inputs == 0, "null argument");
+  const size_t S = ctx->ring_words(), EW = (size_t)ctx->L * 2 * K_lvl * ctx->N_enc, L = (size_t)ctx->L;
+  const size_t n_el = (size_t)batch * NE;
+  auto empty = [&](size_t e) { return h_empty && h_empty[e]; };
+  std::vector<int> budget(n_el * L, level_bit_count(ctx, K_lvl) - 1);  // an EMPTY element keeps the budget of a noiseless ciphertext
+  std::vector<unsigned long long> h((size_t)batch * VERIFY_WORDS);
+  unsigned long long skip4 = 0;
+  bool any_empty = false;
+  for (size_t e = 0; e < n_el; e++) any_empty = any_empty || empty(e);
+  if (SCHEME == 1)
+    for (int b = 0; b < batch; b++)
+      if (empty((size_t)b * NE + 8)) skip4 |= 1ull << b;  // rinocchio.tcc:199-206, 283-288
+  {
+    WsScope ws_scope(ctx, st);
+    uint64_t *dec = (uint64_t *)ws_get(ctx, WS_VERIFY_BATCH, (n_el * S + h.size()) * sizeof(uint64_t));
+    unsigned long long *rep = reinterpret_cast<unsigned long long *>(dec + n_el * S);
+    if (any_empty) RS_HIP(hipMemsetAsync(dec, 0, n_el * S * sizeof(uint64_t), st));
+    // the runs of non-EMPTY elements of the flattened batch: without EMPTY elements one decode of all of them
+    for (size_t e = 0; e < n_el;) {
+      if (empty(e)) {
+        e++;
+        continue;
+      }
+      size_t n = 1;
+      while (e + n < n_el && !empty(e + n)) n++;
+      decode_held(ctx, K_lvl, vk->sk, d_proofs + e * EW, n, dec + e * S, budget.data() + e * L, st);
+      e += n;
+    }
+    VerifyArgs a{};
+    for (int w = 0; w < 3; w++) a.io[w] = vk->io[w];
+    a.Zt = vk->Zt;
+    for (int e = 0; e < 5; e++) a.el[e] = vk->el[e];
+    a.primary = d_primary;
+    a.dec = dec;
+    a.n_inputs = (unsigned)vk->n_inputs;
+    RS_HIP(hipMemsetAsync(rep, 0, h.size() * sizeof(unsigned long long), st));
+    dispatch_arith(ctx, [&](auto tag) { verify_batch_run<decltype(tag), SCHEME>(ctx, a, batch, skip4, rep, st); });
+    RS_HIP(hipMemcpyAsync(h.data(), rep, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    RS_HIP(hipStreamSynchronize(st));
   }
-  out.accepted = out.failed == 0 ? 1u : 0u;
-  if (h[0] != ~0ull) {
-    const size_t idx = (size_t)(h[0] % S);
-    out.first_check = (uint32_t)(h[0] / S);
-    out.first_limb = (uint32_t)(idx / (size_t)ctx->N);
-    out.first_slot = (uint32_t)(idx % (size_t)ctx->N);
-    out.lhs = h[7];
-    out.rhs = h[8];
+  for (int b = 0; b < batch; b++) {
+    const int *bb = budget.data() + (size_t)b * NE * L;
+    const int lowest = *std::min_element(bb, bb + NE * L);
+    const unsigned long long *hb = h.data() + (size_t)b * VERIFY_WORDS;
+    // a proof with a spent budget went through the kernels like the others; its report is not given out
+    h_status[b] = lowest <= 0 ? RS_ERR_NOISE : RS_OK;
+    h_reports[b] = lowest <= 0 ? rs_verify_report{} : report_of(ctx, hb, NC, hb[0] != 0ull, ~hb[0]);
+    if (h_budget_min) h_budget_min[b] = lowest;
   }
-  *h_report = out;
 }
 
 extern "C" {
@@ -597,6 +832,24 @@ int rs_rinocchio_verify_level(rs_ctx *ctx, const rs_rinocchio_vk *vk, int K_lvl,
                               const int *h_empty, rs_verify_report *h_report, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
   verify<1>(ctx, K_lvl, vk_of(vk), d_primary, d_proof, h_empty, h_report, S(stream));
+  RS_API_END
+}
+
+// verify_batch.h
+int rs_verify_batch_group(void) { return VERIFY_PB; }
+
+int rs_groth16_verify_batch(rs_ctx *ctx, const rs_groth16_vk *vk, int K_lvl, int batch, const uint64_t *d_primary, const uint64_t *d_proofs,
+                            const int *h_empty, int *h_status, int *h_budget_min, rs_verify_report *h_reports, rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  verify_batch<0>(ctx, vk_of(vk), K_lvl, batch, d_primary, d_proofs, h_empty, h_status, h_budget_min, h_reports, S(stream));
+  RS_API_END
+}
+
+int rs_rinocchio_verify_batch(rs_ctx *ctx, const rs_rinocchio_vk *vk, int K_lvl, int batch, const uint64_t *d_primary,
+                              const uint64_t *d_proofs, const int *h_empty, int *h_status, int *h_budget_min, rs_verify_report *h_reports,
+                              rs_stream stream) {
+  RS_API_BEGIN_CTX(ctx)
+  verify_batch<1>(ctx, vk_of(vk), K_lvl, batch, d_primary, d_proofs, h_empty, h_status, h_budget_min, h_reports, S(stream));
   RS_API_END
 }
 

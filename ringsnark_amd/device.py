@@ -142,6 +142,16 @@ class VerifyResult(collections.namedtuple("VerifyResult", "accepted failed n_bad
         return bool(self.accepted)
 
 
+class BatchVerdict(collections.namedtuple("BatchVerdict", "result noise_spent budget_min")):
+    """One member of a batched verification (ringsnark_amd/verify_batch.h): result is the member's VerifyResult, or None
+    when its noise budget is spent (noise_spent; the single verifier raises RS_ERR_NOISE there); budget_min is the smallest
+    noise budget over its non-EMPTY ciphertexts.  True when the proof is accepted."""
+    __slots__ = ()
+
+    def __bool__(self):
+        return self.result is not None and bool(self.result.accepted)
+
+
 class BitsResult(collections.namedtuple("BitsResult", "n_bad first_elem first_limb first_slot word value")):
     """rs_bits_report (ringsnark_amd/bits.h), field for field; true when no position is bad."""
     __slots__ = ()
@@ -348,6 +358,50 @@ class Device:
         level: as in groth16_verify (rs_rinocchio_verify_level)."""
         fn = self.lib.rs_rinocchio_verify if level is None else self.lib.rs_rinocchio_verify_level
         return self._verify(fn, vk, "rinocchio", 9, primary, proof, empty, level)
+
+    # ---- a batch of proofs against one key (ringsnark_amd/verify_batch.h)
+    def _stacked(self, items, words, what):
+        """a list of tensors, or one stacked tensor [B][...], as one contiguous tensor and its count B"""
+        t = items if isinstance(items, torch.Tensor) else torch.stack([x.contiguous() for x in items])
+        t = t.contiguous()
+        assert t.numel() % words == 0, "%s: not a whole number of members" % what
+        return t, t.numel() // words
+
+    def _verify_batch(self, fn, vk, scheme, n_elems, primaries, proofs, empties, level):
+        assert vk.scheme == scheme and vk.h, "not a live %s verification key" % scheme
+        K_lvl = self.K if level is None else int(level)
+        proofs, B = self._stacked(proofs, n_elems * self.level_words(K_lvl), "proofs")
+        if vk.n_inputs:
+            primaries, Bp = self._stacked(primaries, vk.n_inputs * self.ring_words, "primary inputs")
+            assert Bp == B, "as many primary inputs as proofs"
+        assert empties is None or len(empties) == B
+        out = []
+        for b0 in range(0, B, _lib.VERIFY_BATCH_MAX):
+            nb = min(_lib.VERIFY_BATCH_MAX, B - b0)
+            em = None if empties is None else (C.c_int * (nb * n_elems))(*[int(e) for row in empties[b0:b0 + nb] for e in row])
+            status, budget, reps = (C.c_int * nb)(), (C.c_int * nb)(), (_lib.VerifyReport * nb)()
+            prim = C.c_void_p(primaries.data_ptr() + 8 * b0 * vk.n_inputs * self.ring_words) if vk.n_inputs else None
+            prf = C.c_void_p(proofs.data_ptr() + 8 * b0 * n_elems * self.level_words(K_lvl))
+            _lib.check(fn(self.h, vk.h, K_lvl, nb, prim, prf, em, status, budget, reps, self.stream()))
+            for b in range(nb):
+                r = reps[b]
+                res = None if status[b] != _lib.RS_OK else VerifyResult(bool(r.accepted), int(r.failed), tuple(int(x) for x in r.n_bad),
+                                                                        int(r.first_check), int(r.first_limb), int(r.first_slot),
+                                                                        int(r.lhs), int(r.rhs))
+                out.append(BatchVerdict(res, status[b] == _lib.RS_ERR_NOISE, int(budget[b])))
+        return out
+
+    def groth16_verify_batch(self, vk, primaries, proofs, empties=None, level=None):
+        """rs_groth16_verify_batch: B proofs ([3] encoding elements each) with their primary inputs against one key, as lists
+        or stacked tensors [B][...]; empties: B lists of 3 flags, or None.  A list of B BatchVerdict: member b's result is the
+        VerifyResult groth16_verify gives for it alone, or None with noise_spent set where that call raises RS_ERR_NOISE.
+        level: every proof was switched to that many primes.  More than 64 members: successive calls."""
+        return self._verify_batch(self.lib.rs_groth16_verify_batch, vk, "groth16", 3, primaries, proofs, empties, level)
+
+    def rinocchio_verify_batch(self, vk, primaries, proofs, empties=None, level=None):
+        """rs_rinocchio_verify_batch: as groth16_verify_batch with [9] elements and 9 flags per member; a member whose
+        element 8 is EMPTY skips check 4, its neighbours do not."""
+        return self._verify_batch(self.lib.rs_rinocchio_verify_batch, vk, "rinocchio", 9, primaries, proofs, empties, level)
 
     # ---- mod-switched encodings (ringsnark_amd/modswitch.h): level = number of leading primes an encoding still has
     def level_words(self, level=None):
