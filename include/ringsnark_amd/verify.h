@@ -67,8 +67,8 @@ typedef struct rs_verify_report {
  * element (its payload is not read).  The other elements are decoded as rs_enc_decode does, noise guard on: a spent
  * budget returns RS_ERR_NOISE with the reference's message -- the reference's verifier throws there too
  * (seal_ring.tcc:446-454).  Returns RS_OK whether the proof is accepted or rejected: a rejection is an answer, not an
- * error.  A key is bound to the context it was created on (RS_ERR_INVALID otherwise).  Calls on one key serialise.
- * Synchronise. */
+ * error.  A key is bound to the context it was created on (RS_ERR_INVALID otherwise) and is only read; calls on one
+ * context serialise.  Synchronise. */
 int rs_groth16_verify(rs_ctx *ctx, const rs_groth16_vk *vk, const uint64_t *d_primary, const uint64_t *d_proof,
                       const int *h_empty /* [3] or NULL */, rs_verify_report *h_report, rs_stream stream);
 int rs_rinocchio_verify(rs_ctx *ctx, const rs_rinocchio_vk *vk, const uint64_t *d_primary, const uint64_t *d_proof,

@@ -41,7 +41,7 @@ int rs_verify_batch_group(void);
  * polynomial is zero (the largest value the budget can take).
  * A key of another context or of the other scheme, or a null argument: RS_ERR_INVALID, nothing written.
  * The decoded elements and the report words live in the context's workspace: calls on one context serialise, and the
- * per-key buffers of the single verifiers are not touched.  Synchronises. */
+ * key is only read.  Synchronises. */
 int rs_groth16_verify_batch(rs_ctx *ctx, const rs_groth16_vk *vk, int K_lvl, int batch, const uint64_t *d_primary,
                             const uint64_t *d_proofs, const int *h_empty, int *h_status, int *h_budget_min,
                             rs_verify_report *h_reports, rs_stream stream);

@@ -266,11 +266,11 @@ static int noise_thresholds(const rs_ctx *ctx, int K, std::vector<uint64_t> &thr
 
 using namespace rs;
 
-// rs::decode_impl (declared in rs_internal.hpp, defined below; modswitch.hip and verify.hip call it too):
+// rs::decode_impl (declared in rs_internal.hpp, defined below; modswitch.hip calls it too):
 // EncodingElem::decode and Decryptor::invariant_noise_budget share everything up to the centred composition.
 // d_rings == nullptr: budgets only.  h_budget [count * L] (may be null).  Throws RS_ERR_NOISE -- after writing every
 // decoding -- when d_rings is given and a ciphertext has no budget left (seal_ring.tcc:446-454).  rs::decode_held is the same
-// body for a caller that holds the context's lock and reads the verdict from h_budget instead (verify.hip, a batch of proofs).
+// body for a caller that holds the context's lock and reads the verdict from h_budget instead (verify.hip).
 // K: the level -- the first K primes of the context, d_enc [count][L][2][K][N_enc]; below ctx->K the decoding is
 // multiplied by the level factor (modswitch.h).
 extern "C" {
@@ -291,6 +291,14 @@ int rs_enc_noise_budget(rs_ctx *ctx, const uint64_t *d_sk, const uint64_t *d_enc
 
 }  // extern "C"
 
+// The guard's text for limb `limb` of element `element` of a decode of `count` elements: the reference's message
+// (seal_ring.tcc:450-453; the budget it prints is max(0, .), i.e. 0), exactly, for one element (its decode takes one
+// EncodingElem); a decode of several says which element it was.
+std::string rs::noise_message(int limb, size_t element, size_t count) {
+  return "ciphertext #" + std::to_string(limb) + " has remaining noise budget 0 <= 0" +
+         (count > 1 ? " (element " + std::to_string(element) + " of the batch)" : std::string());
+}
+
 // the guard's verdict on the significant-bit counts the kernels found
 static int noise_verdict(rs_ctx *ctx, const int *d_bits, size_t count, int tb, bool guard, int *h_budget) {
   std::vector<int> bits(count * (size_t)ctx->L);
@@ -301,12 +309,7 @@ static int noise_verdict(rs_ctx *ctx, const int *d_bits, size_t count, int tb, b
     if (h_budget) h_budget[e] = budget;
     if (budget <= 0 && bad < 0) bad = (long long)e;
   }
-  if (guard && bad >= 0) {
-    // the reference's message (seal_ring.tcc:450-453); the budget it prints is max(0, .), i.e. 0
-    // exactly the reference's text for one element (its decode takes one EncodingElem); a batch call says which element it was
-    throw rs::Error(RS_ERR_NOISE, "ciphertext #" + std::to_string((int)(bad % ctx->L)) + " has remaining noise budget 0 <= 0" +
-                                      (count > 1 ? " (element " + std::to_string((size_t)(bad / ctx->L)) + " of the batch)" : std::string()));
-  }
+  if (guard && bad >= 0) throw rs::Error(RS_ERR_NOISE, noise_message((int)(bad % ctx->L), (size_t)(bad / ctx->L), count));
   return RS_OK;
 }
 

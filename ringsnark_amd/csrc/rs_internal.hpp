@@ -157,12 +157,12 @@ enum WsSlot {
   WS_PASS_B,         // launch_h (W2), bc_interp / bc_h (Wc), bc2_interp / bc2_h (Ws), io_eval_run (tile prefixes O): the second transform workspace; as WS_PASS_A
   WS_STAGE_ROWS,     // msm_run: the ring element (1, .., 1) on the call that builds MsmState::d_ones_plain, OR slot-constant values broadcast to ring elements (never both:
                      // sc_native decides; batch_encode_run takes no workspace); decode_impl: decrypted polynomials [count][L][K][N_enc] between its two kernels.
-                     // The verifiers call rs_enc_decode in a scope of its own, the provers never decode.
+                     // The verifiers decode inside their own scope (decode_held), the provers never decode.
   WS_BC_PRODUCTS,    // bc_h, bc2_h: the block products before the H patch, [columns][2M].  A plan is either bc or bc2.
   WS_KEYGEN_STAGE,   // keygen_run (keygen.hip) with a host-resident key: the two staging buffers of encoded tiles, [2][tile] encoding elements (ciphertexts only, nothing secret)
   WS_MODSWITCH_LEVELS,  // mod_switch_run (modswitch.hip): the intermediate levels of a switch of more than one step, two buffers used in turn,
                      // [count][L][2][K_in - 1][N_enc] and [count][L][2][K_in - 2][N_enc]
-  WS_VERIFY_BATCH,   // verify_batch (verify.hip): the decoded elements of every proof of the batch, [batch][3 | 9][L][N], then the report words [batch][VERIFY_WORDS].
+  WS_VERIFY,         // verify_members (verify.hip; one proof is a batch of one): the decoded elements of every proof of the batch, [batch][3 | 9][L][N], then the report words [batch][VERIFY_WORDS].
                      // Taken once, before the decodes of the same scope (decode_held takes WS_NOISE_BITS and WS_STAGE_ROWS only).
   WS_COUNT
 };
@@ -401,9 +401,11 @@ void instance_map_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uint6
 int decode_impl(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
                 rs_stream stream);
 // encoding.hip.  decode_impl for a caller that HOLDS the context's WsScope and wants the noise verdict as data: d_rings and
-// h_budget [count * L] are both written and a spent budget does not throw (verify.hip: a batch of proofs, one verdict each).
+// h_budget [count * L] are both written and a spent budget does not throw (verify.hip: one verdict per proof).
 void decode_held(rs_ctx *ctx, int K, const uint64_t *d_sk, const uint64_t *d_enc, size_t count, uint64_t *d_rings, int *h_budget,
                  hipStream_t st);
+// encoding.hip.  The text of the noise guard (RS_ERR_NOISE) for limb `limb` of element `element` of a decode of `count` elements
+std::string noise_message(int limb, size_t element, size_t count);
 // encoding.hip.  bit_count(Q[0] * .. * Q[K - 1]): rs_enc_noise_budget_level of a ciphertext whose noise polynomial is zero is this - 1
 int level_bit_count(const rs_ctx *ctx, int K);
 // encoding.hip.  The wire format at level K.  deserialize_run: K_want == 0 accepts every level 1..ctx->K and reports it.

@@ -5,7 +5,9 @@
 // Both verifiers evaluate the constraints on `primary || zeros`, interpolate and run Horner at s.  That value is
 //     v_io(s) = sum_{k <= n_inputs} x_k * A_k(s),   A_k(s) = sum_j A[j][k] * u_j(s),   x_0 = 1
 // (interpolation and evaluation are linear, the ring is commutative), so a verification key holds the n_inputs + 1 columns
-// A_k(s), B_k(s), C_k(s) and Z(s), and a verification is a decode plus one small kernel.
+// A_k(s), B_k(s), C_k(s) and Z(s), and a verification is a decode plus one small kernel.  There is one verifier per scheme:
+// verify_members takes a batch of proofs against one key (verify_batch.h), and the single entry points (verify.h,
+// modswitch.h) are a batch of one.  A key is only read; what a call writes lives in the context's workspace.
 //
 // rs_io_eval_at never holds the m Lagrange values of a slot at once.  With d_j = s - j and tiles of IO_TILE rows:
 //   1. tile_prod_kernel   P_t = prod_{j in tile t} d_j                                            [tiles][L][N]
@@ -18,7 +20,6 @@
 // residues): associative and commutative, so the result does not depend on the order of arrival.
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <utility>
 
 #include "../../include/ringsnark_amd/modswitch.h"
@@ -280,16 +281,15 @@ static void io_eval_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, uin
 }
 
 // ---- the verification kernels ----------------------------------------------------------------------------------------
-constexpr int VERIFY_WORDS = 9;  // device side of the report: [0] key of the first failure (all ones: none), [1..6] n_bad, [7] lhs, [8] rhs
+constexpr int VERIFY_WORDS = 9;  // device side of a proof's report: [0] COMPLEMENT of the key of the first failure (zero: none), [1..6] n_bad, [7] lhs, [8] rhs
 
 struct VerifyArgs {
   const uint64_t *io[3];   // [n_inputs+1][S] public columns of A, B, C at s
   const uint64_t *Zt;      // rinocchio
   const uint64_t *el[5];   // groth16: alpha, beta, delta; rinocchio: alpha, beta, r_v, r_w, r_y
-  const uint64_t *primary; // [n_inputs][S]
-  const uint64_t *dec;     // [3 | 9][S] decoded proof elements
+  const uint64_t *primary; // [batch][n_inputs][S]
+  const uint64_t *dec;     // [batch][3 | 9][S] decoded proof elements
   unsigned n_inputs;
-  unsigned skip;           // bit c: check c is not made
 };
 
 // data x data product of two canonical residues (one operand centred, as the dyadic product of rs_core.hip)
@@ -299,8 +299,9 @@ __device__ __forceinline__ typename ArithOf<M>::T mul_cc(typename ArithOf<M>::T 
 }
 
 // A verification of one slot is two parts: the public sums v_io(s), w_io(s), y_io(s) = column 0 + sum_k x_k * column k
-// (canonical residues), and the checks given those sums and the decoded proof elements.  The batch kernel computes the sums
-// of several proofs side by side (verify_batch_kernel) and shares the checks.
+// (canonical residues), and the checks given those sums and the decoded proof elements.  verify_batch_kernel computes the
+// sums of several proofs side by side and then makes the checks of each; its finish kernel does both for one slot of one
+// proof (verify_slot).
 template <class M>
 __device__ __forceinline__ void io_sums(const VerifyArgs &a, const uint64_t *__restrict__ primary, size_t S, size_t i, const M &mod,
                                         typename ArithOf<M>::T (&io)[3]) {
@@ -358,63 +359,6 @@ __device__ __forceinline__ void verify_slot(const VerifyArgs &a, size_t S, size_
   verify_checks<M, SCHEME>(a, a.dec, S, i, mod, io, lhs, rhs);
 }
 
-// A thread owns a slot pair.  An accepted proof issues no atomic.
-template <class M, int SCHEME>
-__global__ void __launch_bounds__(256)
-verify_kernel(VerifyArgs a, int N, size_t S, const M *__restrict__ qmod, unsigned long long *__restrict__ rep) {
-  constexpr int NC = SCHEME == 0 ? 1 : 6;
-  const size_t pair = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned bad[2] = {0u, 0u};
-  if (2 * pair < S) {
-    const M mod = qmod[(2 * pair) / (size_t)N];
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      uint64_t lhs[6], rhs[6];
-      verify_slot<M, SCHEME>(a, S, 2 * pair + h, mod, lhs, rhs);
-#pragma unroll
-      for (int c = 0; c < NC; c++)
-        if (lhs[c] != rhs[c] && !((a.skip >> c) & 1u)) bad[h] |= 1u << c;
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NC; c++) {
-    const bool b0 = (bad[0] >> c) & 1u, b1 = (bad[1] >> c) & 1u;
-    const unsigned long long v0 = __ballot(b0), v1 = __ballot(b1);
-    if ((v0 | v1) == 0ull) continue;  // wave-uniform: the common path ends here
-    // the lanes of a wave hold ascending slot pairs: the lowest failing lane has the wave's smallest position
-    if ((int)(threadIdx.x & 63u) == __ffsll((long long)(v0 | v1)) - 1) {
-      atomicAdd(rep + 1 + c, (unsigned long long)(__popcll(v0) + __popcll(v1)));
-      atomicMin(rep, (unsigned long long)((size_t)c * S + 2 * pair + (b0 ? 0 : 1)));
-    }
-  }
-}
-
-// the two residues at the first failure
-template <class M, int SCHEME>
-__global__ void verify_finish_kernel(VerifyArgs a, int N, size_t S, const M *__restrict__ qmod, unsigned long long *__restrict__ rep) {
-  const unsigned long long key = rep[0];  // final: written by the launch before this one
-  if (threadIdx.x != 0 || key == ~0ull) return;
-  const size_t c = (size_t)(key / S), i = (size_t)(key % S);
-  uint64_t lhs[6] = {0, 0, 0, 0, 0, 0}, rhs[6] = {0, 0, 0, 0, 0, 0};
-  verify_slot<M, SCHEME>(a, S, i, qmod[i / (size_t)N], lhs, rhs);
-  rep[7] = lhs[c];
-  rep[8] = rhs[c];
-}
-
-template <class M, int SCHEME>
-static void verify_run(rs_ctx *ctx, const VerifyArgs &a, unsigned long long *rep, hipStream_t st) {
-  const size_t S = ctx->ring_words();
-  const double cols = 3.0 * (a.n_inputs + 1) + a.n_inputs + (SCHEME == 0 ? 6 : 15);
-  {
-    ProfScope p(ctx, st, SCHEME == 0 ? "groth16_verify" : "rinocchio_verify", cols * S * 8, 7.0 * (3.0 * a.n_inputs + (SCHEME == 0 ? 5 : 10)) * S);
-    hipLaunchKernelGGL((verify_kernel<M, SCHEME>), dim3((unsigned)((S / 2 + 255) / 256)), dim3(256), 0, st, a, ctx->N, S, CtxArith<M>::qmod(ctx), rep);
-  }
-  RS_HIP(hipGetLastError());
-  hipLaunchKernelGGL((verify_finish_kernel<M, SCHEME>), dim3(1), dim3(64), 0, st, a, ctx->N, S, CtxArith<M>::qmod(ctx), rep);
-  RS_HIP(hipGetLastError());
-}
-
-// ---- a batch of proofs against one key (verify_batch.h) ---------------------------------------------------------------
 // Proofs whose public sums a thread carries at once.  A column of the key is read once per VERIFY_PB proofs: per proof
 // (3 (n_inputs + 1) / VERIFY_PB + n_inputs) S words instead of (4 n_inputs + 3) S.  The accumulators are VERIFY_PB x 3 sums x
 // 2 slots 64-bit words (48 VGPRs at 4); the checks that follow, with the other proofs' sums still live, set the kernel's
@@ -442,10 +386,10 @@ __device__ __forceinline__ void ld_pair(const uint64_t *__restrict__ p, bool vec
 }
 
 // a.primary [batch][n_inputs][S], a.dec [batch][3 | 9][S]; rep [batch][VERIFY_WORDS], zero before the launch, word 0 of a
-// proof: the COMPLEMENT of the key of its first failure (zero: none; one memset prepares every word), the others as in the
-// single kernel.  grid (chunks of 256 slot pairs, groups of VERIFY_PB proofs).  As in verify_kernel a thread owns a slot pair
-// and the lanes of a wave hold ascending pairs.  skip4 bit b: check 4 is not made for proof b.  The tail group's guard
-// p < nb is wave-uniform.
+// proof: the COMPLEMENT of the key (check * S + position) of its first failure (zero: none; one memset prepares every
+// word).  grid (chunks of 256 slot pairs, groups of VERIFY_PB proofs).  A thread owns a slot pair and the lanes of a wave
+// hold ascending pairs: the lowest failing lane has the wave's smallest position.  skip4 bit b: check 4 is not made for
+// proof b.  The tail group's guard p < nb is wave-uniform.
 template <class M, int SCHEME>
 __global__ void __launch_bounds__(256)
 verify_batch_kernel(VerifyArgs a, int batch, unsigned long long skip4, int prim_vec, int N, size_t S, const M *__restrict__ qmod,
@@ -541,7 +485,7 @@ verify_batch_finish_kernel(VerifyArgs a, int N, size_t S, const M *__restrict__ 
 }
 
 template <class M, int SCHEME>
-static void verify_batch_run(rs_ctx *ctx, const VerifyArgs &a, int batch, unsigned long long skip4, unsigned long long *rep, hipStream_t st) {
+static void verify_launch(rs_ctx *ctx, const VerifyArgs &a, int batch, unsigned long long skip4, unsigned long long *rep, hipStream_t st) {
   constexpr int NE = SCHEME == 0 ? 3 : 9, NEL = SCHEME == 0 ? 3 : 6;
   const size_t S = ctx->ring_words();
   const int groups = (batch + VERIFY_PB - 1) / VERIFY_PB;
@@ -559,17 +503,15 @@ static void verify_batch_run(rs_ctx *ctx, const VerifyArgs &a, int batch, unsign
   RS_HIP(hipGetLastError());
 }
 
-// A verification key of either scheme: device copies of everything a verification reads.
+// A verification key of either scheme: device copies of everything a verification reads.  No verification writes to it.
 struct VkBase {
   rs_ctx *ctx = nullptr;      // compared at every use, never dereferenced through the key
   int device = 0;
   int scheme = 0;             // 0 groth16, 1 rinocchio
   size_t n_inputs = 0, words = 0;
-  uint64_t *d_mem = nullptr;  // one allocation: io [3][n_inputs+1][S], Zt [S], el [5][S], sk [K][N_enc], dec [9][S], report
+  uint64_t *d_mem = nullptr;  // one allocation: io [3][n_inputs+1][S], Zt [S], el [5][S], sk [K][N_enc]
   uint64_t *io[3] = {nullptr, nullptr, nullptr}, *Zt = nullptr, *el[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  uint64_t *sk = nullptr, *dec = nullptr;
-  unsigned long long *rep = nullptr;
-  std::mutex mu;              // dec and rep are per key: verifications with one key serialise
+  uint64_t *sk = nullptr;
 };
 
 }  // namespace rs
@@ -623,30 +565,27 @@ static void vk_create(rs_ctx *ctx, int scheme, const rs_r1cs *cs, const uint64_t
   vk->device = ctx->device;
   vk->scheme = scheme;
   vk->n_inputs = cs->n_inputs;
-  vk->words = (3 * n_cols + 1 + 5 + 9) * S + sk_words + 16;
+  vk->words = (3 * n_cols + 1 + 5) * S + sk_words;
   RS_HIP(hipMalloc(&vk->d_mem, vk->words * sizeof(uint64_t)));
   uint64_t *p = vk->d_mem;
   for (int w = 0; w < 3; w++, p += n_cols * S) vk->io[w] = p;
   vk->Zt = p, p += S;
   for (int e = 0; e < 5; e++, p += S) vk->el[e] = p;
-  vk->dec = p, p += 9 * S;
-  vk->sk = p, p += sk_words;
-  vk->rep = reinterpret_cast<unsigned long long *>(p);
+  vk->sk = p;
   RS_HIP(hipMemset(vk->d_mem, 0, vk->words * sizeof(uint64_t)));
   for (int e = 0; e < n_el; e++) RS_HIP(hipMemcpy(vk->el[e], el[e], S * sizeof(uint64_t), hipMemcpyDeviceToDevice));
   RS_HIP(hipMemcpy(vk->sk, d_sk, sk_words * sizeof(uint64_t), hipMemcpyDeviceToDevice));
-  if (must_invert) {  // groth16.tcc:162 divides by gamma
-    const int status = rs_ring_inv(ctx, vk->dec, must_invert, 1, nullptr);
+  if (must_invert) {  // groth16.tcc:162 divides by gamma.  The inverse lands in the first column block, which io_eval_at clears and fills next
+    const int status = rs_ring_inv(ctx, vk->io[0], must_invert, 1, nullptr);
     if (status != RS_OK) throw Error(status, rs_last_error());  // RS_ERR_NOT_INVERTIBLE, "element is not invertible in ring"
   }
   io_eval_at(ctx, cs, d_s, vk->io[0], vk->io[1], vk->io[2], vk->Zt, nullptr);
-  RS_HIP(hipMemset(vk->dec, 0, 9 * S * sizeof(uint64_t)));
   guard.p = nullptr;
   *out = reinterpret_cast<VK *>(vk);
 }
 
-// the report from the downloaded words h [VERIFY_WORDS] of one proof; key: (check * S + position) of its first failure
-static rs_verify_report report_of(const rs_ctx *ctx, const unsigned long long *h, int NC, bool has_first, unsigned long long key) {
+// the report from the downloaded words h [VERIFY_WORDS] of one proof
+static rs_verify_report report_of(const rs_ctx *ctx, const unsigned long long *h, int NC) {
   const size_t S = ctx->ring_words();
   rs_verify_report out{};
   for (int c = 0; c < NC; c++) {
@@ -654,7 +593,8 @@ static rs_verify_report report_of(const rs_ctx *ctx, const unsigned long long *h
     if (h[1 + c]) out.failed |= 1u << c;
   }
   out.accepted = out.failed == 0 ? 1u : 0u;
-  if (has_first) {
+  if (h[0] != 0ull) {
+    const unsigned long long key = ~h[0];  // (check * S + position) of the first failure
     const size_t idx = (size_t)(key % S);
     out.first_check = (uint32_t)(key / S);
     out.first_limb = (uint32_t)(idx / (size_t)ctx->N);
@@ -665,66 +605,20 @@ static rs_verify_report report_of(const rs_ctx *ctx, const unsigned long long *h
   return out;
 }
 
-// K_lvl: the level of the proof, d_proof [NE][L][2][K_lvl][N_enc] (ctx->K: an unswitched proof; modswitch.h)
+// The verifier of either scheme (verify.h, modswitch.h, verify_batch.h): `batch` proofs of level K_lvl, d_proofs
+// [batch][NE][L][2][K_lvl][N_enc] (ctx->K: unswitched proofs), against one key; the outputs as verify_batch.h has them.  The
+// decodings and the report words of the whole batch live in the context's workspace, under the context's lock from the first
+// decode to the download.  Returns the noise budgets [batch * NE][L] the verdicts were taken from.
 template <int SCHEME>
-static void verify(rs_ctx *ctx, int K_lvl, const VkBase *cvk, const uint64_t *d_primary, const uint64_t *d_proof, const int *h_empty,
-                   rs_verify_report *h_report, hipStream_t st) {
-  constexpr int NE = SCHEME == 0 ? 3 : 9, NC = SCHEME == 0 ? 1 : 6;
-  RS_REQUIRE(K_lvl >= 1 && K_lvl <= ctx->K, "level out of range: 1 <= K_lvl <= K");
-  RS_REQUIRE(cvk && d_proof && h_report, "null argument");
-  VkBase *vk = const_cast<VkBase *>(cvk);
-  RS_REQUIRE(vk->ctx == ctx, "verification key of another context");
-  RS_REQUIRE(vk->scheme == SCHEME, "verification key of the other scheme");
-  RS_REQUIRE(d_primary || vk->n_inputs == 0, "null argument");
-  const size_t S = ctx->ring_words(), EW = (size_t)ctx->L * 2 * K_lvl * ctx->N_enc;
-  std::lock_guard<std::mutex> lk(vk->mu);
-  // decode the runs of non-EMPTY elements (guard on: a spent budget ends the call as it ends the reference's verifier)
-  for (int e = 0; e < NE;) {
-    if (h_empty && h_empty[e]) {
-      RS_HIP(hipMemsetAsync(vk->dec + (size_t)e * S, 0, S * sizeof(uint64_t), st));
-      e++;
-      continue;
-    }
-    int n = 1;
-    while (e + n < NE && !(h_empty && h_empty[e + n])) n++;
-    decode_impl(ctx, K_lvl, vk->sk, d_proof + (size_t)e * EW, (size_t)n, vk->dec + (size_t)e * S, nullptr, (rs_stream)st);
-    e += n;
-  }
-  VerifyArgs a{};
-  for (int w = 0; w < 3; w++) a.io[w] = vk->io[w];
-  a.Zt = vk->Zt;
-  for (int e = 0; e < 5; e++) a.el[e] = vk->el[e];
-  a.primary = d_primary;
-  a.dec = vk->dec;
-  a.n_inputs = (unsigned)vk->n_inputs;
-  a.skip = (SCHEME == 1 && h_empty && h_empty[8]) ? 1u << 4 : 0u;  // rinocchio.tcc:199-206, 283-288
-  unsigned long long h[VERIFY_WORDS];
-  {
-    WsScope ws_scope(ctx, st);  // enqueueing (and the profile record) is serialised by the context's lock
-    RS_HIP(hipMemsetAsync(vk->rep, 0, sizeof(h), st));
-    RS_HIP(hipMemsetAsync(vk->rep, 0xFF, sizeof(unsigned long long), st));
-    if (SCHEME == 0)
-      dispatch_arith(ctx, [&](auto tag) { verify_run<decltype(tag), 0>(ctx, a, vk->rep, st); });
-    else
-      dispatch_arith(ctx, [&](auto tag) { verify_run<decltype(tag), 1>(ctx, a, vk->rep, st); });
-    RS_HIP(hipMemcpyAsync(h, vk->rep, sizeof(h), hipMemcpyDeviceToHost, st));
-    RS_HIP(hipStreamSynchronize(st));
-  }
-  *h_report = report_of(ctx, h, NC, h[0] != ~0ull, h[0]);
-}
-
-// verify_batch.h.  The decodings and the report words of the whole batch live in the context's workspace, under the
-// context's lock from the first decode to the download: the key is only read.
-template <int SCHEME>
-static void verify_batch(rs_ctx *ctx, const VkBase *vk, int K_lvl, int batch, const uint64_t *d_primary, const uint64_t *d_proofs,
-                         const int *h_empty, int *h_status, int *h_budget_min, rs_verify_report *h_reports, hipStream_t st) {
+static std::vector<int> verify_members(rs_ctx *ctx, const VkBase *vk, int K_lvl, int batch, const uint64_t *d_primary, const uint64_t *d_proofs,
+                                       const int *h_empty, int *h_status, int *h_budget_min, rs_verify_report *h_reports, hipStream_t st) {
   constexpr int NE = SCHEME == 0 ? 3 : 9, NC = SCHEME == 0 ? 1 : 6;
   RS_REQUIRE(K_lvl >= 1 && K_lvl <= ctx->K, "level out of range: 1 <= K_lvl <= K");
   RS_REQUIRE(vk != nullptr, "null argument");
   RS_REQUIRE(vk->ctx == ctx, "verification key of another context");
   RS_REQUIRE(vk->scheme == SCHEME, "verification key of the other scheme");
   RS_REQUIRE(batch >= 0 && batch <= RS_VERIFY_BATCH_MAX, "batch out of range: 0 <= batch <= RS_VERIFY_BATCH_MAX");
-  if (batch == 0) return;
+  if (batch == 0) return {};
   RS_REQUIRE(d_proofs && h_status && h_reports, "null argument");
   RS_REQUIRE(d_primary || vk->n_inputs == 0, "null argument");
   const size_t S = ctx->ring_words(), EW = (size_t)ctx->L * 2 * K_lvl * ctx->N_enc, L = (size_t)ctx->L;
@@ -740,7 +634,7 @@ static void verify_batch(rs_ctx *ctx, const VkBase *vk, int K_lvl, int batch, co
       if (empty((size_t)b * NE + 8)) skip4 |= 1ull << b;  // rinocchio.tcc:199-206, 283-288
   {
     WsScope ws_scope(ctx, st);
-    uint64_t *dec = (uint64_t *)ws_get(ctx, WS_VERIFY_BATCH, (n_el * S + h.size()) * sizeof(uint64_t));
+    uint64_t *dec = (uint64_t *)ws_get(ctx, WS_VERIFY, (n_el * S + h.size()) * sizeof(uint64_t));
     unsigned long long *rep = reinterpret_cast<unsigned long long *>(dec + n_el * S);
     if (any_empty) RS_HIP(hipMemsetAsync(dec, 0, n_el * S * sizeof(uint64_t), st));
     // the runs of non-EMPTY elements of the flattened batch: without EMPTY elements one decode of all of them
@@ -762,19 +656,43 @@ static void verify_batch(rs_ctx *ctx, const VkBase *vk, int K_lvl, int batch, co
     a.dec = dec;
     a.n_inputs = (unsigned)vk->n_inputs;
     RS_HIP(hipMemsetAsync(rep, 0, h.size() * sizeof(unsigned long long), st));
-    dispatch_arith(ctx, [&](auto tag) { verify_batch_run<decltype(tag), SCHEME>(ctx, a, batch, skip4, rep, st); });
+    dispatch_arith(ctx, [&](auto tag) { verify_launch<decltype(tag), SCHEME>(ctx, a, batch, skip4, rep, st); });
     RS_HIP(hipMemcpyAsync(h.data(), rep, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     RS_HIP(hipStreamSynchronize(st));
   }
   for (int b = 0; b < batch; b++) {
     const int *bb = budget.data() + (size_t)b * NE * L;
     const int lowest = *std::min_element(bb, bb + NE * L);
-    const unsigned long long *hb = h.data() + (size_t)b * VERIFY_WORDS;
     // a proof with a spent budget went through the kernels like the others; its report is not given out
     h_status[b] = lowest <= 0 ? RS_ERR_NOISE : RS_OK;
-    h_reports[b] = lowest <= 0 ? rs_verify_report{} : report_of(ctx, hb, NC, hb[0] != 0ull, ~hb[0]);
+    h_reports[b] = lowest <= 0 ? rs_verify_report{} : report_of(ctx, h.data() + (size_t)b * VERIFY_WORDS, NC);
     if (h_budget_min) h_budget_min[b] = lowest;
   }
+  return budget;
+}
+
+// verify.h, modswitch.h: one proof is a batch of one.  A spent budget ends the call as it ends the reference's verifier, with
+// the text the noise guard of rs_enc_decode has for the run of non-EMPTY elements the ciphertext was decoded in, and
+// *h_report is not written.
+template <int SCHEME>
+static void verify(rs_ctx *ctx, int K_lvl, const VkBase *vk, const uint64_t *d_primary, const uint64_t *d_proof, const int *h_empty,
+                   rs_verify_report *h_report, hipStream_t st) {
+  constexpr size_t NE = SCHEME == 0 ? 3 : 9;
+  RS_REQUIRE(h_report != nullptr, "null argument");
+  int status = RS_OK;
+  rs_verify_report report{};
+  const std::vector<int> budget = verify_members<SCHEME>(ctx, vk, K_lvl, 1, d_primary, d_proof, h_empty, &status, nullptr, &report, st);
+  if (status == RS_ERR_NOISE) {
+    auto empty = [&](size_t e) { return h_empty && h_empty[e]; };
+    const size_t L = (size_t)ctx->L;
+    const size_t spent = (size_t)(std::find_if(budget.begin(), budget.end(), [](int b) { return b <= 0; }) - budget.begin());
+    const size_t e = spent / L;  // the element of the first spent (element, limb)
+    size_t e0 = e, e1 = e + 1;   // its run of non-EMPTY elements, [e0, e1)
+    while (e0 > 0 && !empty(e0 - 1)) e0--;
+    while (e1 < NE && !empty(e1)) e1++;
+    throw Error(RS_ERR_NOISE, noise_message((int)(spent % L), e - e0, e1 - e0));
+  }
+  *h_report = report;
 }
 
 extern "C" {
@@ -841,7 +759,7 @@ int rs_verify_batch_group(void) { return VERIFY_PB; }
 int rs_groth16_verify_batch(rs_ctx *ctx, const rs_groth16_vk *vk, int K_lvl, int batch, const uint64_t *d_primary, const uint64_t *d_proofs,
                             const int *h_empty, int *h_status, int *h_budget_min, rs_verify_report *h_reports, rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
-  verify_batch<0>(ctx, vk_of(vk), K_lvl, batch, d_primary, d_proofs, h_empty, h_status, h_budget_min, h_reports, S(stream));
+  verify_members<0>(ctx, vk_of(vk), K_lvl, batch, d_primary, d_proofs, h_empty, h_status, h_budget_min, h_reports, S(stream));
   RS_API_END
 }
 
@@ -849,7 +767,7 @@ int rs_rinocchio_verify_batch(rs_ctx *ctx, const rs_rinocchio_vk *vk, int K_lvl,
                               const uint64_t *d_proofs, const int *h_empty, int *h_status, int *h_budget_min, rs_verify_report *h_reports,
                               rs_stream stream) {
   RS_API_BEGIN_CTX(ctx)
-  verify_batch<1>(ctx, vk_of(vk), K_lvl, batch, d_primary, d_proofs, h_empty, h_status, h_budget_min, h_reports, S(stream));
+  verify_members<1>(ctx, vk_of(vk), K_lvl, batch, d_primary, d_proofs, h_empty, h_status, h_budget_min, h_reports, S(stream));
   RS_API_END
 }
 

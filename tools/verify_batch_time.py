@@ -1,5 +1,6 @@
 """Batched verification (ringsnark_amd/verify_batch.h) on one MI355X: B single calls beside one batch call of B, on the same
-key and the same proofs.  The single verifier is unchanged by the batch entry points, so it is the baseline.
+key and the same proofs.  Both run one verifier body and one kernel pair (verify.hip: a single call is a batch of one), so the
+first column is what a call costs and the ratio what sharing a call, a decode and the key's columns saves.
 
   ringGroth16   C3 (N = N_enc = 8192, L = K = 4), chain circuit m = 64, n_inputs = 2: the decode dominates
   Rinocchio     C5 (N = 2048, L = 1, N_enc = 16384, K = 8), the logistic-regression circuit (256 features, 517 public

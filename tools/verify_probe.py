@@ -5,9 +5,9 @@ Per m:
   io_eval_at      one rs_io_eval_at call (host clock around the call; it synchronises) and the device time of its three
                   kernels from the library's own per-launch events (rs_set_profiling), in a pass of its own
   vk_create       rs_groth16_vk_create (uploads excluded; includes rs_io_eval_at, the unit test of gamma, the copies)
-  verify          rs_groth16_verify on a "proof" of three FRESH encodings of random ring elements (rejected, but the same
-                  work as an accepted one; uniformly random words would trip the noise guard), beside rs_enc_decode of the
-                  same three elements alone
+  verify          rs_groth16_verify (the batch verifier's body and kernel on a batch of one) on a "proof" of three FRESH
+                  encodings of random ring elements (rejected, but the same work as an accepted one; uniformly random words
+                  would trip the noise guard), beside rs_enc_decode of the same three elements alone
   instance_map    rs_instance_map_eval, only where its [m][L][N] intermediates fit (m <= --imap-max-log): the same-run
                   comparison for io_eval_at, with the outputs compared bit for bit
 Warm-up, then medians of --repeats calls; rs_measure_peaks of the same run is recorded as the clock-dependent denominators.
