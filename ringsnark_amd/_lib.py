@@ -249,6 +249,20 @@ VERIFY_BATCH_SIGNATURES = {  # every function of include/ringsnark_amd/verify_ba
     "rs_rinocchio_verify_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                             C.POINTER(VerifyReport), vp]),
 }
+PACKED_SIGNATURES = {  # every function of include/ringsnark_amd/packed.h
+    "rs_enc_pack_bits": (C.c_int, [vp]),
+    "rs_enc_packed_words": (C.c_size_t, [vp]),
+    "rs_enc_pack_c0": (C.c_int, [vp, vp, C.c_size_t, vp, C.POINTER(C.c_size_t), vp]),
+    "rs_enc_unpack_c0": (C.c_int, [vp, vp, C.c_size_t, vp, vp]),
+    "rs_enc_expand_packed": SEEDED_SIGNATURES["rs_enc_expand_seeded"],
+    "rs_groth16_keygen_packed": SEEDED_SIGNATURES["rs_groth16_keygen_seeded"],
+    "rs_rinocchio_keygen_packed": SEEDED_SIGNATURES["rs_rinocchio_keygen_seeded"],
+    "rs_msm_packed": SEEDED_SIGNATURES["rs_msm_seeded"],
+    "rs_groth16_prove_packed": SEEDED_SIGNATURES["rs_groth16_prove_seeded"],
+    "rs_rinocchio_prove_packed": SEEDED_SIGNATURES["rs_rinocchio_prove_seeded"],
+    "rs_groth16_prove_batch_packed": BATCH_SIGNATURES["rs_groth16_prove_batch_seeded"],
+    "rs_rinocchio_prove_batch_packed": BATCH_SIGNATURES["rs_rinocchio_prove_batch_seeded"],
+}
 VERIFY_BATCH_MAX = 64  # RS_VERIFY_BATCH_MAX
 VERIFY_BATCH_GROUP = 4  # rs_verify_batch_group(): proofs whose public sums one thread of the check kernel carries (csrc/verify.hip VERIFY_PB)
 
@@ -267,7 +281,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **SOLVE_SIGNATURES, **VERIFY_SIGNATURES,
                               **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES, **MODSWITCH_SIGNATURES, **BITS_SIGNATURES,
-                              **VERIFY_BATCH_SIGNATURES}.items():
+                              **VERIFY_BATCH_SIGNATURES, **PACKED_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

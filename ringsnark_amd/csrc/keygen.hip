@@ -148,8 +148,39 @@ constexpr size_t KEYGEN_HOST_TILE = 64;  // elements per staging buffer of a hos
 // the kernel of the next one.  Ordering as msm_run's host-key tiles, the directions reversed: the copy stream waits for
 // ev_encoded[buf] (the kernel filled the buffer), the kernel that refills the buffer waits for ev_drained[buf].
 // pub, compact: as encode_linear; the tiles and copies of a compact vector are half the size.
+// packed (with compact; packed.h): every tile of at most `tile` elements is encoded compact into the FIRST staging buffer and
+// packed from there by pack_c0_kernel on `st` -- a device-resident vector straight into its place (it never exists
+// unpacked), a host-resident one into a second pair of buffers behind the two compact ones, [2][tile] packed elements, which
+// the copy stream drains under the same two events (ev_encoded: the tile is packed).  One compact buffer serves: the kernel
+// that refills it follows the pack kernel that read it on `st`.
 static void encode_vector(rs_ctx *ctx, LinRows lf, const uint64_t *d_sk, size_t count, uint64_t seed, uint64_t pub, bool compact,
-                          uint64_t *dst, bool to_host, size_t tile, uint64_t *stage, hipStream_t st) {
+                          bool packed, uint64_t *dst, bool to_host, size_t tile, uint64_t *stage, hipStream_t st) {
+  if (packed) {
+    KeygenState &kg = ctx->keygen;
+    const size_t S = ctx->ring_words(), PW = packed_words(ctx);
+    uint64_t *const pstage = stage + 2 * tile * (ctx->enc_words() / 2);
+    int tile_idx = 0;
+    for (size_t t0 = 0; t0 < count; t0 += tile, tile_idx++) {
+      const int buf = tile_idx & 1;
+      const size_t tt = std::min(tile, count - t0);
+      LinRows part = lf;
+      for (int r = 0; r < lf.R; r++) part.rows[r] = lf.rows[r] + t0 * S;
+      encode_linear(ctx, part, d_sk, tt, seed + t0, pub + t0, true, stage, st);
+      if (!to_host) {
+        pack_c0_run(ctx, stage, tt, dst + t0 * PW, nullptr, st);
+        continue;
+      }
+      uint64_t *d_tile = pstage + (size_t)buf * tile * PW;
+      if (tile_idx >= 2) RS_HIP(hipStreamWaitEvent(st, kg.ev_drained[buf], 0));  // the copy of tile - 2 has left the buffer
+      pack_c0_run(ctx, stage, tt, d_tile, nullptr, st);
+      RS_HIP(hipEventRecord(kg.ev_encoded[buf], st));
+      RS_HIP(hipStreamWaitEvent(kg.copy_stream, kg.ev_encoded[buf], 0));
+      RS_HIP(hipMemcpyAsync(dst + t0 * PW, d_tile, tt * PW * sizeof(uint64_t), hipMemcpyDeviceToHost, kg.copy_stream));
+      RS_HIP(hipEventRecord(kg.ev_drained[buf], kg.copy_stream));
+    }
+    if (to_host) RS_HIP(hipStreamSynchronize(kg.copy_stream));
+    return;
+  }
   if (!to_host) {
     encode_linear(ctx, lf, d_sk, count, seed, pub, compact, dst, st);
     return;
@@ -207,10 +238,12 @@ struct KeyVector {
 
 // SCHEME 0: groth16 (trap = alpha, beta, delta), 1: rinocchio (trap = alpha, beta, r_v, r_w, r_y).
 // dst: the scheme's outputs in the order of h_seeds.  h_pub != nullptr: a seeded key (seeded.h) -- the three vectors compact,
-// a of every element from the public stream h_pub[v] + k.
+// a of every element from the public stream h_pub[v] + k; packed: those three vectors bit-packed (packed.h), tiled by `tile`
+// wherever they live.
 template <int SCHEME>
 static void keygen_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, const uint64_t *const *trap, const uint64_t *d_sk,
-                       const uint64_t *h_seeds, const uint64_t *h_pub, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st) {
+                       const uint64_t *h_seeds, const uint64_t *h_pub, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st,
+                       bool packed) {
   constexpr int NV = SCHEME == 0 ? 5 : 6, NT = SCHEME == 0 ? 3 : 5;
   RS_REQUIRE(cs && d_s && d_sk && h_seeds, "null argument");
   for (int e = 0; e < NT; e++) RS_REQUIRE(trap[e] != nullptr, "null argument");
@@ -231,8 +264,9 @@ static void keygen_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, cons
       for (int w = 0; w < v; w++)
         RS_REQUIRE(!ranges_meet(h_pub[v], len[v], h_pub[w], len[w]),
                    "public seed ranges of two key vectors intersect: their elements would share the polynomial a");
-  if (host_key && tile == 0) tile = KEYGEN_HOST_TILE;
-  if (host_key) RS_REQUIRE(tile * (size_t)ctx->L < ((size_t)1 << 31), "tile too large");
+  RS_REQUIRE(h_pub || !packed, "a packed key is a seeded key");
+  if ((host_key || packed) && tile == 0) tile = KEYGEN_HOST_TILE;
+  if (host_key || packed) RS_REQUIRE(tile * (size_t)ctx->L < ((size_t)1 << 31), "tile too large");
 
   // scratch: At, Bt, Ct [n1], Ht [m+1], Zt, and 7 coefficient elements
   SecretScratch sc;
@@ -280,9 +314,12 @@ static void keygen_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, cons
   {
     WsScope ws_scope(ctx, st);
     uint64_t *stage = nullptr;
+    if (packed)  // the two compact buffers of a seeded key (the first is used), then [2][tile] packed elements for a host-resident key
+      stage = (uint64_t *)ws_get(ctx, WS_KEYGEN_STAGE, 2 * tile * (ctx->enc_words() / 2 + (host_key ? packed_words(ctx) : 0)) * sizeof(uint64_t));
     if (host_key) {
       KeygenState &kg = ctx->keygen;
-      stage = (uint64_t *)ws_get(ctx, WS_KEYGEN_STAGE, 2 * tile * (h_pub ? ctx->enc_words() / 2 : ctx->enc_words()) * sizeof(uint64_t));
+      if (!packed)
+        stage = (uint64_t *)ws_get(ctx, WS_KEYGEN_STAGE, 2 * tile * (h_pub ? ctx->enc_words() / 2 : ctx->enc_words()) * sizeof(uint64_t));
       if (!kg.copy_stream) RS_HIP(hipStreamCreateWithFlags(&kg.copy_stream, hipStreamNonBlocking));
       for (int b = 0; b < 2; b++) {  // each by its own null test: a call that failed half way is completed by the next
         if (!kg.ev_encoded[b]) RS_HIP(hipEventCreateWithFlags(&kg.ev_encoded[b], hipEventDisableTiming));
@@ -290,19 +327,20 @@ static void keygen_run(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, cons
       }
     }
     for (int v = 0; v < NV; v++)
-      encode_vector(ctx, vec[v].lf, d_sk, vec[v].count, h_seeds[v], h_pub ? h_pub[v] : h_seeds[v], h_pub && vec[v].big, vec[v].dst,
-                    host_key && vec[v].big, tile, stage, st);
+      encode_vector(ctx, vec[v].lf, d_sk, vec[v].count, h_seeds[v], h_pub ? h_pub[v] : h_seeds[v], h_pub && vec[v].big, packed && vec[v].big,
+                    vec[v].dst, host_key && vec[v].big, tile, stage, st);
     RS_HIP(hipStreamSynchronize(st));
   }
 }
 
 
 void keygen_run_scheme(int scheme, rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, const uint64_t *const *trap, const uint64_t *d_sk,
-                       const uint64_t *h_seeds, const uint64_t *h_pub, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st) {
+                       const uint64_t *h_seeds, const uint64_t *h_pub, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st,
+                       bool packed) {
   if (scheme == 0)
-    keygen_run<0>(ctx, cs, d_s, trap, d_sk, h_seeds, h_pub, dst, host_key, tile, st);
+    keygen_run<0>(ctx, cs, d_s, trap, d_sk, h_seeds, h_pub, dst, host_key, tile, st, packed);
   else
-    keygen_run<1>(ctx, cs, d_s, trap, d_sk, h_seeds, h_pub, dst, host_key, tile, st);
+    keygen_run<1>(ctx, cs, d_s, trap, d_sk, h_seeds, h_pub, dst, host_key, tile, st, packed);
 }
 
 }  // namespace rs
@@ -318,7 +356,7 @@ int rs_groth16_keygen(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, const
   RS_REQUIRE(out != nullptr, "null argument");
   const uint64_t *trap[3] = {d_alpha, d_beta, d_delta};
   uint64_t *dst[5] = {out->s_pows, out->delta_ts, out->delta_mid, out->d_alpha, out->d_beta};
-  keygen_run<0>(ctx, cs, d_s, trap, d_sk, h_seeds, nullptr, dst, out->host_key != 0, out->tile, S(stream));
+  keygen_run<0>(ctx, cs, d_s, trap, d_sk, h_seeds, nullptr, dst, out->host_key != 0, out->tile, S(stream), false);
   RS_API_END
 }
 
@@ -329,7 +367,7 @@ int rs_rinocchio_keygen(rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, con
   RS_REQUIRE(out != nullptr, "null argument");
   const uint64_t *trap[5] = {d_alpha, d_beta, d_rv, d_rw, d_ry};
   uint64_t *dst[6] = {out->s_pows, out->alpha_s_pows, out->beta_prods, out->d_beta_rv_ts, out->d_beta_rw_ts, out->d_beta_ry_ts};
-  keygen_run<1>(ctx, cs, d_s, trap, d_sk, h_seeds, nullptr, dst, out->host_key != 0, out->tile, S(stream));
+  keygen_run<1>(ctx, cs, d_s, trap, d_sk, h_seeds, nullptr, dst, out->host_key != 0, out->tile, S(stream), false);
   RS_API_END
 }
 

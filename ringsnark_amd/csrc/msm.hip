@@ -315,8 +315,12 @@ static void msm_run_arith(rs_ctx *ctx, const MsmKey &key, const rs_msm_vec *vecs
   // expand_seeded_tile_kernel on `st`, between ev_copied and the tile's kernels, and everything downstream reads the staging
   // buffer as it does for a host-resident key.  A host-resident seeded key lands in two compact buffers behind the staging
   // buffers (half their size) first; a device-resident one is expanded from where it lies, with no copy and no event.
-  const bool seeded = pub_seeds != nullptr, staged = crs_on_host || seeded;
-  const size_t key_words = seeded ? enc_words / 2 : enc_words;  // words of a stored element
+  // Packed key (key.packed, packed.h): a seeded key whose stored element is packed_words() words -- in the pointer arithmetic,
+  // in the copy of a tile and in the landing buffers, which keep their compact size and stride -- and whose tiles are expanded
+  // by expand_packed_tile_kernel in the same place.
+  const bool seeded = pub_seeds != nullptr, staged = crs_on_host || seeded, packed = seeded && key.packed;
+  RS_REQUIRE(seeded || !key.packed, "a packed key is a seeded key");
+  const size_t key_words = packed ? packed_words(ctx) : seeded ? enc_words / 2 : enc_words;  // words of a stored element
   uint64_t *stage = nullptr, *land = nullptr;
   const MsmGeometry geo = msm_geometry(ctx, key, n_groups, Tmax, wide_blocks);
   const size_t tile_terms = geo.tile_terms, stage_words = geo.stage_words;
@@ -415,8 +419,8 @@ static void msm_run_arith(rs_ctx *ctx, const MsmKey &key, const rs_msm_vec *vecs
     }
     if (seeded)  // c1 of the tile's elements from their STORED indices (t0 + i) % crs_window; the landing buffer is the tile in order
       for (int c = 0; c < n_crs; c++)
-        expand_seeded_run(ctx, crs_on_host ? land_at(tile_idx & 1, c) : d_crs[c], crs_on_host, pub_seeds[c], t0, crs_window, tt,
-                          stage_at(tile_idx & 1, c), st);
+        (packed ? expand_packed_run : expand_seeded_run)(ctx, crs_on_host ? land_at(tile_idx & 1, c) : d_crs[c], crs_on_host, pub_seeds[c], t0,
+                                                         crs_window, tt, stage_at(tile_idx & 1, c), st);
     double rows_in = 0;  // coefficient rows (term, limb) read by this tile
     for (int v = 0; v < n_vecs; v++) rows_in += (double)(vecs[v].T > t0 ? std::min(tt, vecs[v].T - t0) : 0) * L;
     // plaintext rows, MAX_GROUPS groups per launch (one launch for the calls of up to MAX_GROUPS groups)

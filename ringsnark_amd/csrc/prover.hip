@@ -103,14 +103,15 @@ static ProveLayout prove_layout(const rs_ctx *ctx, const rs_r1cs *cs, int scheme
   return {(4 * m + 1) * ctx->ring_words(), 2 * (4 * b + 1) + b + 1, 2, {{2, 4 * B + 1, m + 1, b * (4 * m + 1) + m + 1, m + 1}, aux, {}}};
 }
 
-// The key vectors of a proving key in the order of the public seeds `pub` of a seeded one (nullptr: a full key)
+// The key vectors of a proving key in the order of the public seeds `pub` of a seeded one (nullptr: a full key); packed: the
+// mark of packed.h beside them
 struct ProverKey {
   const uint64_t *vecs[3];
   const uint64_t *pub;
   size_t window;
-  bool on_host;
+  bool on_host, packed;
   // vectors k .. k + n - 1, of len elements, as the key side of a pass
-  MsmKey at(int k, int n, size_t len) const { return MsmKey{vecs + k, n, len, window, on_host, pub ? pub + k : nullptr}; }
+  MsmKey at(int k, int n, size_t len) const { return MsmKey{vecs + k, n, len, window, on_host, pub ? pub + k : nullptr, packed}; }
 };
 
 static void require_members(int batch, const uint64_t *const *d_assignments, bool batched) {
@@ -124,7 +125,7 @@ static void require_members(int batch, const uint64_t *const *d_assignments, boo
 // h_kinds: nullptr or [B][n_vars]; d_proofs [B][3], h_empty nullptr or [B][3].
 void groth16_prove_members(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *pub, int B,
                            const uint64_t *const *d_assignments, const uint8_t *h_kinds, uint64_t *d_proofs, int *h_empty, bool batched,
-                           hipStream_t st) {
+                           hipStream_t st, bool packed) {
   require_members(B, d_assignments, batched);
   RS_REQUIRE(ctx && cs && pk && d_proofs, "null argument");
   RS_REQUIRE(pk->d_s_pows && pk->d_delta_ts && pk->d_alpha && pk->d_beta, "incomplete proving key");
@@ -133,7 +134,7 @@ void groth16_prove_members(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *
   RS_REQUIRE(n_aux == 0 || pk->d_delta_mid, "delta_mid missing");
   WsScope ws_scope(ctx, st);
   const ProveLayout lay = prove_layout(ctx, cs, 0, B);
-  const ProverKey key{{pk->d_s_pows, pk->d_delta_ts, pk->d_delta_mid}, pub, pk->window, pk->host_key != 0};
+  const ProverKey key{{pk->d_s_pows, pk->d_delta_ts, pk->d_delta_mid}, pub, pk->window, pk->host_key != 0, packed};
   memset(&ctx->timings, 0, sizeof(ctx->timings));
   PhaseTimer pt(ctx, st);
   pt.mark(0);
@@ -228,7 +229,7 @@ void groth16_prove_members(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *
 // [B][3] array of batch.h).  h_kinds: nullptr or [B][n_vars]; d_proofs [B][9], h_empty nullptr or [B][9].
 void rinocchio_prove_members(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *pub, int B,
                              const uint64_t *const *d_assignments, const uint8_t *h_kinds, const uint64_t *const d[3], uint64_t *d_proofs,
-                             int *h_empty, bool batched, hipStream_t st) {
+                             int *h_empty, bool batched, hipStream_t st, bool packed) {
   require_members(B, d_assignments, batched);
   RS_REQUIRE(ctx && cs && pk && d_proofs, "null argument");
   RS_REQUIRE(pk->d_s_pows && pk->d_alpha_s_pows, "incomplete proving key");
@@ -240,7 +241,7 @@ void rinocchio_prove_members(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_
   RS_REQUIRE(!zk || n_aux == 0 || (pk->d_beta_rv_ts && pk->d_beta_rw_ts && pk->d_beta_ry_ts), "beta_r*_ts missing");
   WsScope ws_scope(ctx, st);
   const ProveLayout lay = prove_layout(ctx, cs, 1, B);
-  const ProverKey key{{pk->d_s_pows, pk->d_alpha_s_pows, pk->d_beta_prods}, pub, pk->window, pk->host_key != 0};
+  const ProverKey key{{pk->d_s_pows, pk->d_alpha_s_pows, pk->d_beta_prods}, pub, pk->window, pk->host_key != 0, packed};
   const int NG = lay.pass[0].n_groups;
   auto dk = [&](int b, int k) { return zk ? d[k] + (size_t)3 * b * rw : nullptr; };
   memset(&ctx->timings, 0, sizeof(ctx->timings));

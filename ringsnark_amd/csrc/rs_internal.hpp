@@ -159,7 +159,8 @@ enum WsSlot {
                      // sc_native decides; batch_encode_run takes no workspace); decode_impl: decrypted polynomials [count][L][K][N_enc] between its two kernels.
                      // The verifiers decode inside their own scope (decode_held), the provers never decode.
   WS_BC_PRODUCTS,    // bc_h, bc2_h: the block products before the H patch, [columns][2M].  A plan is either bc or bc2.
-  WS_KEYGEN_STAGE,   // keygen_run (keygen.hip) with a host-resident key: the two staging buffers of encoded tiles, [2][tile] encoding elements (ciphertexts only, nothing secret)
+  WS_KEYGEN_STAGE,   // keygen_run (keygen.hip) with a host-resident key: the two staging buffers of encoded tiles, [2][tile] encoding elements (ciphertexts only, nothing secret);
+                     // with a packed key (packed.h), host-resident or not: [2][tile] compact elements, then [2][tile] packed elements for a host-resident one
   WS_MODSWITCH_LEVELS,  // mod_switch_run (modswitch.hip): the intermediate levels of a switch of more than one step, two buffers used in turn,
                      // [count][L][2][K_in - 1][N_enc] and [count][L][2][K_in - 2][N_enc]
   WS_VERIFY,         // verify_members (verify.hip; one proof is a batch of one): the decoded elements of every proof of the batch, [batch][3 | 9][L][N], then the report words [batch][VERIFY_WORDS].
@@ -357,6 +358,7 @@ struct MsmKey {
   size_t window;                         // != 0: `window` elements are stored and element t lives at index t % window (tiled keys, ringsnark_amd.h)
   bool on_host = false;                  // host-resident: streamed tile by tile
   const uint64_t *pub_seeds = nullptr;   // [n] public seeds: the vectors are compact, c0 only (seeded.h)
+  bool packed = false;                   // with pub_seeds: the c0 rows are bit-packed, rs_enc_packed_words words an element (packed.h)
 };
 // A coefficient vector of an inner product given as a linear form instead of rows: vector[t] = sum_e lv_e[t] * r_{k_e}
 // (slot-wise), lv_e[t] = Lcols[(col_e * L + limb) * Mlen + t] slot-constant scalars and r_0 = 1, r_k = k-th ring element of
@@ -424,27 +426,62 @@ __device__ __forceinline__ uint64_t splitmix_at(uint64_t seed, uint64_t k) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
+// z % Q without a division (a run-time 64-bit divisor compiles to a long sequence): with h = hi64(z mu), mu = floor(2^64 / Q),
+// z / Q - 2 < h <= z / Q, so r = z - h Q is in [0, 3 Q) -- below 2^64 for Q < 2^62 -- and two conditional subtractions
+// leave z % Q exactly.
+__device__ __forceinline__ uint64_t barrett_mod(uint64_t z, uint64_t Q, uint64_t mu) {
+  uint64_t r = z - __umul64hi(z, mu) * Q;
+  r = r >= Q ? r - Q : r;
+  return r >= Q ? r - Q : r;
+}
 #endif
+// Q_j and mu_j = floor(2^64 / Q_j) of the context's data primes: the argument of the kernels that regenerate c1 (seeded.hip, packed.hip)
+struct ExpandPrimes {
+  uint64_t Q[RS_MAX_K], mu[RS_MAX_K];
+};
+inline ExpandPrimes expand_primes(const rs_ctx *ctx) {
+  ExpandPrimes pr{};
+  for (int j = 0; j < ctx->K; j++) {
+    RS_REQUIRE(ctx->Q[j] < (1ull << 62), "data prime out of range");
+    pr.Q[j] = ctx->Q[j];
+    pr.mu[j] = (uint64_t)((((unsigned __int128)1) << 64) / ctx->Q[j]);
+  }
+  return pr;
+}
+constexpr int EXPAND_THREADS = 256;
+constexpr int EXPAND_SPAN = 2048;  // coefficients per workgroup: four 16-byte accesses per thread and component
 // seeded.hip.  count full-format elements at dst from compact c0 blocks: c0 copied, c1 regenerated (seeded.h).  Element i has
 // STORED index (first + i) % window (window == 0: first + i), which numbers its stream; its c0 is element i of `c0`
 // (linear: a landing buffer, a caller's slice) or element <stored index> of it (the whole vector of a device-resident key).
 void expand_seeded_run(rs_ctx *ctx, const uint64_t *c0, bool linear, uint64_t pub_seed, size_t first, size_t window, size_t count,
                        uint64_t *dst, hipStream_t st);
+// packed.hip (packed.h).  Width w, words of a packed row and of a packed element of the context
+int pack_bits(const rs_ctx *ctx);
+size_t packed_row_words(const rs_ctx *ctx);
+inline size_t packed_words(const rs_ctx *ctx) { return (size_t)ctx->L * ctx->K * packed_row_words(ctx); }
+// count compact elements -> packed elements; d_bad: nullptr, or a zeroed device word that counts the input words >= 2^w
+void pack_c0_run(rs_ctx *ctx, const uint64_t *c0, size_t count, uint64_t *packed, unsigned long long *d_bad, hipStream_t st);
+// expand_seeded_run with bit-packed c0 rows at `packed`
+void expand_packed_run(rs_ctx *ctx, const uint64_t *packed, bool linear, uint64_t pub_seed, size_t first, size_t window, size_t count,
+                       uint64_t *dst, hipStream_t st);
 // keygen.hip.  The body of the generators: scheme 0 groth16 (5 seeds, 3 trapdoor elements), 1 rinocchio (6, 5); dst in the
-// order of h_seeds; h_pub != nullptr: a seeded key.  Takes the context's WsScope itself.
+// order of h_seeds; h_pub != nullptr: a seeded key; packed (with h_pub): its three vectors bit-packed (packed.h).  Takes the
+// context's WsScope itself.
 void keygen_run_scheme(int scheme, rs_ctx *ctx, const rs_r1cs *cs, const uint64_t *d_s, const uint64_t *const *trap, const uint64_t *d_sk,
-                       const uint64_t *h_seeds, const uint64_t *h_pub, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st);
+                       const uint64_t *h_seeds, const uint64_t *h_pub, uint64_t *const *dst, bool host_key, size_t tile, hipStream_t st,
+                       bool packed = false);
 // prover.hip.  The body of every ringGroth16 / Rinocchio proving entry point: B assignments against one key, one pass per
 // key vector.  batched: false from the single-proof entry points (B == 1), true from those of include/ringsnark_amd/batch.h,
-// whatever B.  pub != nullptr: the three vectors of pk are compact and pub holds their public seeds (seeded.h).  h_kinds
+// whatever B.  pub != nullptr: the three vectors of pk are compact and pub holds their public seeds (seeded.h); packed: they
+// are bit-packed as well (packed.h).  h_kinds
 // [B][n_vars] or nullptr; d: d1, d2, d3 of member 0 (all null: not zero knowledge), member b's 3 b ring elements further.
 // They take the context's WsScope themselves.
 void groth16_prove_members(rs_ctx *ctx, const rs_r1cs *cs, const rs_groth16_pk *pk, const uint64_t *pub, int B,
                            const uint64_t *const *d_assignments, const uint8_t *h_kinds, uint64_t *d_proofs, int *h_empty, bool batched,
-                           hipStream_t st);
+                           hipStream_t st, bool packed = false);
 void rinocchio_prove_members(rs_ctx *ctx, const rs_r1cs *cs, const rs_rinocchio_pk *pk, const uint64_t *pub, int B,
                              const uint64_t *const *d_assignments, const uint8_t *h_kinds, const uint64_t *const d[3], uint64_t *d_proofs,
-                             int *h_empty, bool batched, hipStream_t st);
+                             int *h_empty, bool batched, hipStream_t st, bool packed = false);
 // witness_plan.hip
 const uint64_t *witness_Z_rows(rs_ctx *ctx, size_t m);
 void witness_plans_destroy(rs_ctx *ctx);  // every plan of the context (rs_ctx_destroy)

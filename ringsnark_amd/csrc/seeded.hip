@@ -10,23 +10,6 @@
 
 namespace rs {
 
-// Q_j and mu_j = floor(2^64 / Q_j) of the context's data primes
-struct ExpandPrimes {
-  uint64_t Q[RS_MAX_K], mu[RS_MAX_K];
-};
-
-// z % Q without a division (a run-time 64-bit divisor compiles to a long sequence): with h = hi64(z mu), mu = floor(2^64 / Q),
-// z / Q - 2 < h <= z / Q, so r = z - h Q is in [0, 3 Q) -- below 2^64 for Q < 2^62 -- and two conditional subtractions
-// leave z % Q exactly.
-__device__ __forceinline__ uint64_t barrett_mod(uint64_t z, uint64_t Q, uint64_t mu) {
-  uint64_t r = z - __umul64hi(z, mu) * Q;
-  r = r >= Q ? r - Q : r;
-  return r >= Q ? r - Q : r;
-}
-
-constexpr int EXPAND_THREADS = 256;
-constexpr int EXPAND_SPAN = 2048;  // coefficients per workgroup: four 16-byte accesses per thread and component
-
 // One workgroup per (element, limb, prime) row, or per EXPAND_SPAN coefficients of it: Q_j and the stream seed are uniform
 // in the workgroup.  c0 moves in 16-byte words; c1 is two draws per 16-byte store.
 // enc: [count][L][2][K][n].  c0: [.][L][K][n], element i read at index i (linear) or at its stored index.
@@ -64,12 +47,7 @@ void expand_seeded_run(rs_ctx *ctx, const uint64_t *c0, bool linear, uint64_t pu
   RS_REQUIRE(((uintptr_t)c0 | (uintptr_t)dst) % 16 == 0, "seeded key vectors and their expansion must be 16-byte aligned");
   const size_t blocks = count * (size_t)ctx->L * ctx->K * parts;
   RS_REQUIRE(blocks < ((size_t)1 << 31), "too many elements for one launch");
-  ExpandPrimes pr{};
-  for (int j = 0; j < ctx->K; j++) {
-    RS_REQUIRE(ctx->Q[j] < (1ull << 62), "data prime out of range");
-    pr.Q[j] = ctx->Q[j];
-    pr.mu[j] = (uint64_t)((((unsigned __int128)1) << 64) / ctx->Q[j]);
-  }
+  const ExpandPrimes pr = expand_primes(ctx);
   const double words = (double)count * (double)ctx->enc_words();
   // algorithmic bytes: c0 read, both components written; no FP64 work
   ProfScope p(ctx, st, "expand_seeded_tile_kernel", words * 8.0 * 1.5, 0.0);

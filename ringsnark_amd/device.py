@@ -431,11 +431,52 @@ class Device:
         assert len(seeds) == n, (len(seeds), n)
         return (C.c_uint64 * n)(*[(int(x) * 65537) % 2**64 for x in seeds])
 
-    def _key_vector(self, count, host, seeded=False):
-        """seeded: the compact layout [count][L][K][N_enc] (ringsnark_amd/seeded.h)"""
+    def _key_vector(self, count, host, seeded=False, packed=False):
+        """seeded: the compact layout [count][L][K][N_enc] (ringsnark_amd/seeded.h); packed: [count][L][K][row_words]
+        (ringsnark_amd/packed.h)"""
         if host:
-            return self.host_alloc(max(count, 1) * (self.enc_words // 2 if seeded else self.enc_words))
-        return self.c0_empty(count) if seeded else self.enc_empty(count)
+            return self.host_alloc(max(count, 1) * (self.packed_words if packed else self.enc_words // 2 if seeded else self.enc_words))
+        return self.packed_empty(count) if packed else self.c0_empty(count) if seeded else self.enc_empty(count)
+
+    # ---- bit-packed seeded keys (ringsnark_amd/packed.h)
+    @property
+    def pack_bits(self):
+        return int(self.lib.rs_enc_pack_bits(self.h))
+
+    @property
+    def packed_words(self):
+        """words of one packed element, L K row_words"""
+        return int(self.lib.rs_enc_packed_words(self.h))
+
+    def packed_empty(self, *lead):
+        return torch.empty(tuple(lead) + (self.L, self.K, self.packed_words // (self.L * self.K)), dtype=torch.int64, device=self.device)
+
+    def enc_pack_c0(self, c0, want_bad=True):
+        """rs_enc_pack_c0: compact elements [count][L][K][N_enc] -> (packed elements [count][L][K][row_words], the number of
+        input words >= 2^w -- their low w bits are stored -- or None without want_bad)"""
+        assert c0.is_contiguous()
+        count = self._count(c0, self.enc_words // 2)
+        out = self.packed_empty(count) if c0.dim() > 3 else self.packed_empty()
+        bad = C.c_size_t(0)
+        _lib.check(self.lib.rs_enc_pack_c0(self.h, _ptr(c0), count, _ptr(out), C.byref(bad) if want_bad else None, self.stream()))
+        return out, (int(bad.value) if want_bad else None)
+
+    def enc_unpack_c0(self, packed):
+        """rs_enc_unpack_c0: packed elements -> compact elements"""
+        assert packed.is_contiguous()
+        count = self._count(packed, self.packed_words)
+        out = self.c0_empty(count) if packed.dim() > 3 else self.c0_empty()
+        _lib.check(self.lib.rs_enc_unpack_c0(self.h, _ptr(packed), count, _ptr(out), self.stream()))
+        return out
+
+    def enc_expand_packed(self, packed, pub_seed, first=0):
+        """rs_enc_expand_packed: enc_expand_seeded on packed elements (c0 unpacked, c1 regenerated)"""
+        assert packed.is_contiguous()
+        count = self._count(packed, self.packed_words)
+        out = self.enc_empty(count) if packed.dim() > 3 else self.enc_empty()
+        _lib.check(self.lib.rs_enc_expand_packed(self.h, _ptr(packed), C.c_uint64((pub_seed * 65537) % 2**64), first, count, _ptr(out),
+                                                 self.stream()))
+        return out
 
     def c0_empty(self, *lead):
         return torch.empty(tuple(lead) + (self.L, self.K, self.N_enc), dtype=torch.int64, device=self.device)
@@ -485,58 +526,73 @@ class Device:
                                                  self.stream()))
         return out
 
-    def groth16_keygen(self, dcs, vk, seeds=None, host=False, tile=0, seeded=False, pub_seeds=None, allow_shared_seeds=False):
+    def groth16_keygen(self, dcs, vk, seeds=None, host=False, tile=0, seeded=False, pub_seeds=None, allow_shared_seeds=False,
+                       packed=False):
         """groth16::generator (groth16.tcc:5-66) on the device: the proving key of the trapdoor `vk` (the dict groth16_vk
         takes: s, alpha, beta, gamma, delta, sk), as the dict groth16_prove accepts.  seeds: None, one integer, or five
         (s_pows, delta_ts, delta_mid, alpha, beta) in enc_encode's convention; their ranges must not intersect.
         host: the three vectors are HostWords (a key larger than HBM), encoded in tiles of `tile` elements.
         seeded: a seeded key (ringsnark_amd/seeded.h) -- the three vectors compact [count][L][K][N_enc] (half the size), and
         "pub_seeds": the five public seeds their c1 halves are regenerated from (pub_seeds: None = drawn from `secrets`, one
-        integer, or five); groth16_prove and enc_expand_seeded take them from the dict."""
+        integer, or five); groth16_prove and enc_expand_seeded take them from the dict.
+        packed (with seeded; ValueError otherwise): the three vectors bit-packed [count][L][K][row_words]
+        (ringsnark_amd/packed.h), and "packed": True beside "pub_seeds"; the provers and msm dispatch on that mark."""
+        if packed and not seeded:
+            raise ValueError("packed=True needs seeded=True: a packed key is a seeded key (ringsnark_amd/packed.h)")
         t = {k: self._vk_part(vk[k]) for k in ("s", "alpha", "beta", "delta", "sk")}
         m, n_aux = dcs.m, dcs.n_vars - dcs.n_inputs
         if seeded:
             pub, pub_words = self._public_seeds(seeds, pub_seeds, [m + 1, m + 1, n_aux, 1, 1], allow_shared_seeds)
         self.sync()
-        pk = dict(s_pows=self._key_vector(m + 1, host, seeded), delta_ts=self._key_vector(m + 1, host, seeded),
-                  delta_mid=self._key_vector(n_aux, host, seeded) if n_aux else None, alpha=self.enc_empty(), beta=self.enc_empty())
+        pk = dict(s_pows=self._key_vector(m + 1, host, seeded, packed), delta_ts=self._key_vector(m + 1, host, seeded, packed),
+                  delta_mid=self._key_vector(n_aux, host, seeded, packed) if n_aux else None, alpha=self.enc_empty(), beta=self.enc_empty())
         addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
         members = (addr(pk["s_pows"]), addr(pk["delta_ts"]), addr(pk["delta_mid"]), pk["alpha"].data_ptr(), pk["beta"].data_ptr(),
                    1 if host else 0, tile)
         args = [self.h, dcs.h, _ptr(t["s"]), _ptr(t["alpha"]), _ptr(t["beta"]), _ptr(t["delta"]), _ptr(t["sk"]), self._keygen_seeds(seeds, 5)]
         if seeded:
             out = _lib.Groth16SeededKeyOut(*members)
-            _lib.check(self.lib.rs_groth16_keygen_seeded(*args, pub_words, C.byref(out), self.stream()))
+            keygen = self.lib.rs_groth16_keygen_packed if packed else self.lib.rs_groth16_keygen_seeded
+            _lib.check(keygen(*args, pub_words, C.byref(out), self.stream()))
             pk["pub_seeds"] = pub
+            if packed:
+                pk["packed"] = True
         else:
             out = _lib.Groth16KeyOut(*members)
             _lib.check(self.lib.rs_groth16_keygen(*args, C.byref(out), self.stream()))
         return pk
 
     def rinocchio_keygen(self, dcs, vk, seeds=None, host=False, tile=0, seeded=False, pub_seeds=None, allow_shared_seeds=False,
-                         into=None):
+                         into=None, packed=False):
         """rinocchio::generator (rinocchio.tcc:5-72): the dict rinocchio_prove accepts, from the dict rinocchio_vk takes.
         seeds: s_pows, alpha_s_pows, beta_prods, beta_rv_ts, beta_rw_ts, beta_ry_ts.  seeded, pub_seeds, allow_shared_seeds:
-        as in groth16_keygen (six public seeds).  into: a key this call returned for the same system, `host` and `seeded`,
-        whose buffers are written again instead of new ones (a host-resident key is tens of GiB of page-locked memory)."""
+        as in groth16_keygen (six public seeds).  into: a key this call returned for the same system, `host`, `seeded` and
+        `packed`, whose buffers are written again instead of new ones (a host-resident key is tens of GiB of page-locked
+        memory).  packed: as in groth16_keygen."""
+        if packed and not seeded:
+            raise ValueError("packed=True needs seeded=True: a packed key is a seeded key (ringsnark_amd/packed.h)")
         t = {k: self._vk_part(vk[k]) for k in ("s", "alpha", "beta", "r_v", "r_w", "r_y", "sk")}
         m, n_aux = dcs.m, dcs.n_vars - dcs.n_inputs
         if seeded:
             pub, pub_words = self._public_seeds(seeds, pub_seeds, [m + 1, m + 1, n_aux, 1, 1, 1], allow_shared_seeds)
         self.sync()
         pk = into if into is not None else dict(
-            s_pows=self._key_vector(m + 1, host, seeded), alpha_s_pows=self._key_vector(m + 1, host, seeded),
-            beta_prods=self._key_vector(n_aux, host, seeded) if n_aux else None, beta_rv_ts=self.enc_empty(),
+            s_pows=self._key_vector(m + 1, host, seeded, packed), alpha_s_pows=self._key_vector(m + 1, host, seeded, packed),
+            beta_prods=self._key_vector(n_aux, host, seeded, packed) if n_aux else None, beta_rv_ts=self.enc_empty(),
             beta_rw_ts=self.enc_empty(), beta_ry_ts=self.enc_empty())
         assert isinstance(pk["s_pows"], HostWords) == bool(host) and ("pub_seeds" in pk) == bool(seeded and into is not None)
+        assert bool(pk.get("packed")) == bool(packed and into is not None)
         addr = lambda v: None if v is None else (v.ptr if isinstance(v, HostWords) else v.data_ptr())
         members = (addr(pk["s_pows"]), addr(pk["alpha_s_pows"]), addr(pk["beta_prods"]), pk["beta_rv_ts"].data_ptr(),
                    pk["beta_rw_ts"].data_ptr(), pk["beta_ry_ts"].data_ptr(), 1 if host else 0, tile)
         args = [self.h, dcs.h] + [_ptr(t[k]) for k in ("s", "alpha", "beta", "r_v", "r_w", "r_y", "sk")] + [self._keygen_seeds(seeds, 6)]
         if seeded:
             out = _lib.RinocchioSeededKeyOut(*members)
-            _lib.check(self.lib.rs_rinocchio_keygen_seeded(*args, pub_words, C.byref(out), self.stream()))
+            keygen = self.lib.rs_rinocchio_keygen_packed if packed else self.lib.rs_rinocchio_keygen_seeded
+            _lib.check(keygen(*args, pub_words, C.byref(out), self.stream()))
             pk["pub_seeds"] = pub
+            if packed:
+                pk["packed"] = True
         else:
             out = _lib.RinocchioKeyOut(*members)
             _lib.check(self.lib.rs_rinocchio_keygen(*args, C.byref(out), self.stream()))
@@ -641,16 +697,19 @@ class Device:
                                              C.byref(used) if want_used else None, self.stream()))
         return out, int(used.value)
 
-    def msm(self, crs_list, vecs, n_groups, want_used=False, crs_len=None, window=0, pub_seeds=None):
+    def msm(self, crs_list, vecs, n_groups, want_used=False, crs_len=None, window=0, pub_seeds=None, packed=False):
         """vecs: list of (coeff tensor [T][L][N], kinds or None, group) or, for a SLOT-CONSTANT vector (one value per
         (term, limb) in every slot: coefficients_for_Z), (tensor [T][L], kinds, group, True).  window != 0: the CRS tensors hold
         `window` elements and logical element t is read from t % window (crs_len = logical length).
         CRS vectors given as HostWords (host_alloc) are streamed from host memory (rs_msm_hostkey).
-        pub_seeds (one per CRS vector, as a seeded key's "pub_seeds" holds them): the CRS vectors are COMPACT (rs_msm_seeded)."""
+        pub_seeds (one per CRS vector, as a seeded key's "pub_seeds" holds them): the CRS vectors are COMPACT (rs_msm_seeded);
+        packed (with pub_seeds, as a packed key's "packed" mark): they are bit-packed (rs_msm_packed)."""
+        if packed and pub_seeds is None:
+            raise ValueError("packed=True needs pub_seeds: a packed key is a seeded key")
         n_crs = len(crs_list)
         on_host = isinstance(crs_list[0], HostWords)
         assert all(isinstance(c, HostWords) == on_host for c in crs_list)
-        key_words = self.enc_words if pub_seeds is None else self.enc_words // 2
+        key_words = self.enc_words if pub_seeds is None else self.packed_words if packed else self.enc_words // 2
         if crs_len is None:
             crs_len = crs_list[0].words // key_words if on_host else self._count(crs_list[0], key_words)
         crs = (C.c_void_p * n_crs)(*[(c.ptr if on_host else c.data_ptr()) for c in crs_list])
@@ -672,8 +731,9 @@ class Device:
         used = (C.c_size_t * len(vecs))()
         if pub_seeds is not None:
             assert len(pub_seeds) == n_crs
-            _lib.check(self.lib.rs_msm_seeded(self.h, crs, self._keygen_seeds(list(pub_seeds), n_crs), 1 if on_host else 0, n_crs, crs_len,
-                                              window, mv, len(vecs), n_groups, _ptr(out), used if want_used else None, self.stream()))
+            fn = self.lib.rs_msm_packed if packed else self.lib.rs_msm_seeded
+            _lib.check(fn(self.h, crs, self._keygen_seeds(list(pub_seeds), n_crs), 1 if on_host else 0, n_crs, crs_len,
+                          window, mv, len(vecs), n_groups, _ptr(out), used if want_used else None, self.stream()))
             return out, [int(u) for u in used]
         fn = self.lib.rs_msm_hostkey if on_host else self.lib.rs_msm
         _lib.check(fn(self.h, crs, n_crs, crs_len, window, mv, len(vecs), n_groups, _ptr(out), used if want_used else None, self.stream()))
@@ -868,7 +928,7 @@ class Device:
         proof = self.enc_empty(3)
         empty = (C.c_int * 3)()
         keep, kp = self._kinds(kinds, dcs.n_vars)
-        prove = self.lib.rs_groth16_prove_seeded if seeded else self.lib.rs_groth16_prove_kinds
+        prove = self._prover(pk, "rs_groth16_prove_kinds", "rs_groth16_prove_seeded", "rs_groth16_prove_packed")
         _lib.check(prove(self.h, dcs.h, C.byref(s), _ptr(assignment), kp, _ptr(proof), empty if want_empty else None, self.stream()))
         return proof, [int(e) for e in empty]
 
@@ -880,9 +940,16 @@ class Device:
         proof = self.enc_empty(9)
         empty = (C.c_int * 9)()
         keep, kp = self._kinds(kinds, dcs.n_vars)
-        prove = self.lib.rs_rinocchio_prove_seeded if seeded else self.lib.rs_rinocchio_prove_kinds
+        prove = self._prover(pk, "rs_rinocchio_prove_kinds", "rs_rinocchio_prove_seeded", "rs_rinocchio_prove_packed")
         _lib.check(prove(self.h, dcs.h, C.byref(s), _ptr(assignment), kp, _ptr(d1), _ptr(d2), _ptr(d3), _ptr(proof), empty, self.stream()))
         return proof, [int(e) for e in empty]
+
+    def _prover(self, pk, full, seeded, packed):
+        """the entry point for a key dictionary: "packed" (with "pub_seeds") a packed key, "pub_seeds" a seeded key"""
+        if pk.get("packed"):
+            assert "pub_seeds" in pk, "a packed key is a seeded key"
+            return getattr(self.lib, packed)
+        return getattr(self.lib, seeded if "pub_seeds" in pk else full)
 
     # ---- batched proving (include/ringsnark_amd/batch.h)
     def _groth16_key(self, pk, window):
@@ -936,7 +1003,7 @@ class Device:
         s, seeded = self._groth16_key(pk, window)
         proofs = self.enc_empty(max(B, 1), 3)
         empty = (C.c_int * (3 * max(B, 1)))()
-        prove = self.lib.rs_groth16_prove_batch_seeded if seeded else self.lib.rs_groth16_prove_batch
+        prove = self._prover(pk, "rs_groth16_prove_batch", "rs_groth16_prove_batch_seeded", "rs_groth16_prove_batch_packed")
         _lib.check(prove(self.h, dcs.h, C.byref(s), B, ptrs, kp, _ptr(proofs), empty, self.stream()))
         return proofs, [[int(empty[3 * b + k]) for k in range(3)] for b in range(B)]
 
@@ -949,7 +1016,7 @@ class Device:
         s, seeded = self._rinocchio_key(pk, window)
         proofs = self.enc_empty(max(B, 1), 9)
         empty = (C.c_int * (9 * max(B, 1)))()
-        prove = self.lib.rs_rinocchio_prove_batch_seeded if seeded else self.lib.rs_rinocchio_prove_batch
+        prove = self._prover(pk, "rs_rinocchio_prove_batch", "rs_rinocchio_prove_batch_seeded", "rs_rinocchio_prove_batch_packed")
         _lib.check(prove(self.h, dcs.h, C.byref(s), B, ptrs, kp, _ptr(d), _ptr(proofs), empty, self.stream()))
         return proofs, [[int(empty[9 * b + k]) for k in range(9)] for b in range(B)]
 
