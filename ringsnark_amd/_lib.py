@@ -249,6 +249,10 @@ VERIFY_BATCH_SIGNATURES = {  # every function of include/ringsnark_amd/verify_ba
     "rs_rinocchio_verify_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                             C.POINTER(VerifyReport), vp]),
 }
+R1CS_BATCH_SIGNATURES = {  # every function of include/ringsnark_amd/r1cs_batch.h
+    "rs_r1cs_solve_batch": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), C.c_int, C.POINTER(SolveStats), vp]),
+    "rs_r1cs_check_batch": (C.c_int, [vp, vp, C.c_int, C.POINTER(vp), vp, C.POINTER(R1csReport), vp]),
+}
 PACKED_SIGNATURES = {  # every function of include/ringsnark_amd/packed.h
     "rs_enc_pack_bits": (C.c_int, [vp]),
     "rs_enc_packed_words": (C.c_size_t, [vp]),
@@ -281,7 +285,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **SOLVE_SIGNATURES, **VERIFY_SIGNATURES,
                               **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES, **MODSWITCH_SIGNATURES, **BITS_SIGNATURES,
-                              **VERIFY_BATCH_SIGNATURES, **PACKED_SIGNATURES}.items():
+                              **VERIFY_BATCH_SIGNATURES, **PACKED_SIGNATURES, **R1CS_BATCH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "../../include/ringsnark_amd/r1cs_solve.h"
+#include "r1cs_solve_plan.hpp"
 #include "witness_eval.hpp"
 
 namespace rs {
@@ -117,28 +118,6 @@ solve_walk_kernel(const SolveCsr<typename ArithOf<M>::T> cs, const uint32_t *__r
     solve_step<M>(cs, cur, asg, S, pair, limb, mod);
   }
 }
-
-// one kernel launch of a solve: kind 0 = the level kernel on one level, 1 = the walk kernel on a run of levels
-struct SolveLaunch {
-  int kind;
-  size_t s_lo, s_hi;
-  double bytes, ops;  // ProfScope: algorithmic bytes and FP64 instructions per lane
-};
-
-}  // namespace rs
-
-struct rs_r1cs_solve_plan {
-  rs_ctx *ctx = nullptr;
-  const rs_r1cs *cs = nullptr;
-  rs_r1cs_solve_info info{};
-  std::vector<uint32_t> rows, wires;  // the steps, ordered by (level, constraint)
-  std::vector<uint64_t> level_ptr;    // [n_levels + 1]
-  std::vector<rs::SolveLaunch> launches[3];  // by mode
-  uint32_t *d_rows = nullptr, *d_wires = nullptr;
-  uint64_t *d_kinv = nullptr;  // [L][n_steps] constants of the context's arithmetic
-};
-
-namespace rs {
 
 // The schedule of r1cs_solve.h.  k: the coefficient sum of every step, [n_steps][L] canonical.
 static void build_schedule(const rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *h_given, rs_r1cs_solve_plan *P, std::vector<uint64_t> &k) {

@@ -780,6 +780,40 @@ class Device:
         _lib.check(self.lib.rs_r1cs_solve(self.h, plan.h, _ptr(assignment), SOLVE_MODES[mode], C.byref(stats), self.stream()))
         return SolveStats(int(stats.level_launches), int(stats.walk_launches))
 
+    def r1cs_solve_batch(self, plan, assignments, mode="auto", allow_partial=False):
+        """r1cs_solve for B assignments (a list of device tensors [n_vars][L][N], 1 <= B <= 8, no two overlapping) of one
+        plan in one pass over the schedule and the system (rs_r1cs_solve_batch): every member ends word for word as
+        r1cs_solve leaves it.  Returns SolveStats of the whole batch, equal to those of one r1cs_solve call."""
+        assignments = list(assignments)
+        for a in assignments:
+            assert self._count(a, self.ring_words) == plan.dcs.n_vars, "the solver addresses every row of the assignment"
+        i = plan.info
+        if i.n_unsolved and not allow_partial:
+            raise ValueError("the given wires do not determine the assignment: %d of %d variables unsolved, first unsolved variable %d; "
+                             "first blocked constraint %d: %s" % (i.n_unsolved, plan.dcs.n_vars, i.first_unsolved, i.first_blocked,
+                                                                  SOLVE_BLOCKED[i.blocked_reason]))
+        B = len(assignments)
+        ptrs = (C.c_void_p * max(B, 1))(*[a.data_ptr() for a in assignments])
+        stats = _lib.SolveStats()
+        _lib.check(self.lib.rs_r1cs_solve_batch(self.h, plan.h, B, ptrs, SOLVE_MODES[mode], C.byref(stats), self.stream()))
+        return SolveStats(int(stats.level_launches), int(stats.walk_launches))
+
+    def r1cs_check_batch(self, dcs, assignments, want_flags=False):
+        """r1cs_check for B FULL assignments (1 <= B <= 8; members may alias) in one pass over the three matrices
+        (rs_r1cs_check_batch): one main and one epilogue launch, one download.  Returns a list of R1csCheck, member b's equal to
+        r1cs_check of it; want_flags: .flags of member b is row b of one uint8 tensor [B][m]."""
+        assignments = list(assignments)
+        for a in assignments:
+            assert self._count(a, self.ring_words) == dcs.n_vars, "the check reads every row of the assignment"
+        B = len(assignments)
+        ptrs = (C.c_void_p * max(B, 1))(*[a.data_ptr() for a in assignments])
+        flags = torch.empty((max(B, 1), dcs.m), dtype=torch.uint8, device=self.device) if want_flags else None
+        reps = (_lib.R1csReport * max(B, 1))()
+        _lib.check(self.lib.rs_r1cs_check_batch(self.h, dcs.h, B, ptrs, None if flags is None else C.c_void_p(flags.data_ptr()), reps,
+                                                self.stream()))
+        return [R1csCheck(int(r.n_violated), int(r.first_row), int(r.first_limb), int(r.first_slot), int(r.a), int(r.b), int(r.c),
+                          None if flags is None else flags[b]) for b, r in enumerate(reps[:B])]
+
     def ring_bit_decompose(self, x, nbits, out=None, x_stride=1, bits_stride=None, want_report=True):
         """The bit rows of ring elements whose slots hold one integer below 2^nbits in every limb (rs_ring_bit_decompose).
         x: a tensor whose element e is the ring element at x_stride * e ring elements (x_stride = 1: [count][L][N]); bit k
@@ -813,8 +847,8 @@ class Device:
                                          want_report=want_report)
         return rep
 
-    def _require_satisfied(self, dcs, assignment):
-        r = self.r1cs_check(dcs, assignment)
+    def _require_satisfied(self, dcs, assignment, report=None):
+        r = self.r1cs_check(dcs, assignment) if report is None else report
         if not r.satisfied:
             raise ValueError("assignment does not satisfy the constraint system: %d of %d constraints violated, first constraint %d "
                              "at limb %d, slot %d (a = %d, b = %d, c = %d)"
@@ -979,9 +1013,11 @@ class Device:
         assignments = list(assignments)
         B = len(assignments)
         if check:
+            # one pass over the system for the whole batch (a batch the provers refuse anyway: member by member, as before)
+            reports = self.r1cs_check_batch(dcs, assignments) if 1 <= B <= 8 else [None] * B
             for b, a in enumerate(assignments):
                 try:
-                    self._require_satisfied(dcs, a)
+                    self._require_satisfied(dcs, a, reports[b])
                 except ValueError as e:
                     raise ValueError("batch member %d: %s" % (b, e)) from None
         ptrs = (C.c_void_p * max(B, 1))(*[a.data_ptr() for a in assignments])
