@@ -55,38 +55,46 @@ def rin_case(name, m, zk):
     return dict(prm=prm, ctx=ctx, cs=cs, asg=asg, pk=pk, vk=vk, proof=proof, empty=empty, d=d)
 
 
-def io_at_s(ctx, cs, s, primary):
-    """v_io(s), w_io(s), y_io(s) the reference's way (groth16.tcc:131-154): evaluate the constraints on `primary || zeros`,
+def polys_at_s(ctx, cs, s, assignment):
+    """A(s), B(s), C(s) of the three polynomials an assignment of all n_vars wires gives: evaluate the constraints on it,
     interpolate, Horner at s."""
     Rg = S.Ring(ctx)
-    padded = np.zeros((cs.n_vars,) + ctx.ring_shape(), dtype=np.uint64)
-    padded[: cs.n_inputs] = primary
+    assert len(assignment) == cs.n_vars
     ocs = H.oracle_cs(cs)
     out = []
     for which in range(3):
         coeffs = np.empty((cs.m,) + ctx.ring_shape(), dtype=np.uint64)
         for limb, q in enumerate(ctx.q):
-            ev = O.r1cs_evaluate(q, ocs, which, limb, np.ascontiguousarray(padded[:, limb, :]))
+            ev = O.r1cs_evaluate(q, ocs, which, limb, np.ascontiguousarray(assignment[:, limb, :]))
             coeffs[:, limb, :] = O.interpolate(q, ev)
         out.append(S.poly_eval_ring(Rg, coeffs, s))
     return out
 
 
-def g16_sides(ctx, cs, vk, primary, dec):
-    """[(lhs, rhs)] of groth16.tcc:159-169, in the reference's order of operations (division by gamma included)."""
+def io_at_s(ctx, cs, s, primary):
+    """v_io(s), w_io(s), y_io(s) the reference's way (groth16.tcc:131-154): evaluate the constraints on `primary || zeros`,
+    interpolate, Horner at s."""
+    padded = np.zeros((cs.n_vars,) + ctx.ring_shape(), dtype=np.uint64)
+    padded[: cs.n_inputs] = primary
+    return polys_at_s(ctx, cs, s, padded)
+
+
+def g16_sides(ctx, cs, vk, primary, dec, io=None):
+    """[(lhs, rhs)] of groth16.tcc:159-169, in the reference's order of operations (division by gamma included).
+    io: io_at_s(ctx, cs, vk["s"], primary), where the caller has it."""
     Rg = S.Ring(ctx)
-    v, w, y = io_at_s(ctx, cs, vk["s"], primary)
+    v, w, y = io if io is not None else io_at_s(ctx, cs, vk["s"], primary)
     f = Rg.add(Rg.add(Rg.mul(vk["beta"], v), Rg.mul(vk["alpha"], w)), y)
     f = Rg.mul(f, Rg.inv(vk["gamma"]))
     rhs = Rg.add(Rg.add(Rg.mul(vk["alpha"], vk["beta"]), Rg.mul(vk["gamma"], f)), Rg.mul(vk["delta"], dec[2]))
     return [(Rg.mul(dec[0], dec[1]), rhs)]
 
 
-def rin_sides(ctx, cs, vk, primary, dec):
-    """[(lhs, rhs)] of the six comparisons of rinocchio.tcc:223-293, in verify.h's order."""
+def rin_sides(ctx, cs, vk, primary, dec, io=None):
+    """[(lhs, rhs)] of the six comparisons of rinocchio.tcc:223-293, in verify.h's order.  io: as in g16_sides."""
     Rg = S.Ring(ctx)
     V, Vp, W, Wp, Y, Yp, Hh, Hp, Lb = dec
-    v, w, y = io_at_s(ctx, cs, vk["s"], primary)
+    v, w, y = io if io is not None else io_at_s(ctx, cs, vk["s"], primary)
     L = Rg.mul(Rg.add(Rg.add(Rg.mul(V, vk["r_v"]), Rg.mul(W, vk["r_w"])), Rg.mul(Y, vk["r_y"])), vk["beta"])
     Pv = Rg.sub(Rg.mul(Rg.add(V, v), Rg.add(W, w)), Rg.add(Y, y))
     return [(Vp, Rg.mul(V, vk["alpha"])), (Wp, Rg.mul(W, vk["alpha"])), (Yp, Rg.mul(Y, vk["alpha"])), (Hp, Rg.mul(Hh, vk["alpha"])),
