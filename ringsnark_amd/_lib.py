@@ -72,6 +72,12 @@ class VerifyReport(C.Structure):
                 ("first_limb", C.c_uint32), ("first_slot", C.c_uint32), ("lhs", C.c_uint64), ("rhs", C.c_uint64)]
 
 
+class InvReport(C.Structure):
+    _fields_ = [("n_zero", C.c_uint64), ("zero_elem", C.c_uint64), ("zero_limb", C.c_uint32), ("zero_slot", C.c_uint32),
+                ("n_bad", C.c_uint64), ("bad_elem", C.c_uint64), ("bad_limb", C.c_uint32), ("bad_slot", C.c_uint32),
+                ("bad_x", C.c_uint64), ("bad_num", C.c_uint64)]
+
+
 class BitsReport(C.Structure):
     _fields_ = [("n_bad", C.c_uint64), ("first_elem", C.c_uint64), ("first_limb", C.c_uint32), ("first_slot", C.c_uint32),
                 ("word", C.c_uint64), ("value", C.c_uint64)]
@@ -242,6 +248,10 @@ BITS_SIGNATURES = {  # every function of include/ringsnark_amd/bits.h
     "rs_ring_bit_decompose": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(BitsReport), vp]),
 }
 
+INVERSE_SIGNATURES = {  # every function of include/ringsnark_amd/inverse.h
+    "rs_ring_inv_or_zero": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.POINTER(InvReport), vp]),
+}
+
 VERIFY_BATCH_SIGNATURES = {  # every function of include/ringsnark_amd/verify_batch.h
     "rs_verify_batch_group": (C.c_int, []),
     "rs_groth16_verify_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -285,7 +295,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **SOLVE_SIGNATURES, **VERIFY_SIGNATURES,
                               **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES, **MODSWITCH_SIGNATURES, **BITS_SIGNATURES,
-                              **VERIFY_BATCH_SIGNATURES, **PACKED_SIGNATURES, **R1CS_BATCH_SIGNATURES}.items():
+                              **VERIFY_BATCH_SIGNATURES, **PACKED_SIGNATURES, **R1CS_BATCH_SIGNATURES,
+                              **INVERSE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -142,7 +142,7 @@ enum WsSlot {
   WS_SIDE,           // witness_run: interpolated constant parts [3][L][M]; rs_enc_mul_ring: one encoding element (the product before it is copied back).  Two entry points; the msm_run that rs_enc_mul_ring calls does not take it.
   WS_COLUMNS,        // witness_chunk, interpolate_arith: the column-major vectors of a chunk, [vectors][columns][M].  Two entry points.
   WS_BC_SPECTRA,     // bc_h, bc2_h: spectra of the second operand's blocks, [columns][2M | 4M].  A plan is either bc or bc2.
-  WS_SMALL,          // rs_ring_inv, rs_ring_is_zero, normalised_len (poly.hip), rs_r1cs_check, rs_ring_bit_decompose, io_eval_run: flag / report words (io_eval_run: + the constants c_j from byte 256);
+  WS_SMALL,          // rs_ring_inv, rs_ring_is_zero, normalised_len (poly.hip), rs_r1cs_check, rs_ring_bit_decompose, rs_ring_inv_or_zero, io_eval_run: flag / report words (io_eval_run: + the constants c_j from byte 256);
                      // msm_run with a host-resident or a seeded key: the two staging buffers of the key tiles (+ the two compact landing buffers of a host-resident seeded key).  vk_create calls rs_ring_inv and then io_eval_at: two scopes, one after the
                      // other.  normalised_len synchronises before it returns, so its three calls in one scope each take a dead pointer's place.  The provers reach msm_run
                      // after witness_run, which does not take this slot, and nothing else in a prover's scope does.

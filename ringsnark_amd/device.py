@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from .params import RingParams
-from .r1cs import R1CS, SOLVE_BLOCKED, R1csCheck, SolveInfo, given_mask, plaintext_check_layout
+from .r1cs import R1CS, SOLVE_BLOCKED, InvReport, R1csCheck, SolveInfo, given_mask, plaintext_check_layout
 
 
 def to_device(a: np.ndarray, device) -> torch.Tensor:
@@ -846,6 +846,48 @@ class Device:
         _, rep = self.ring_bit_decompose(rows[first + logT:], logT, out=rows[first:], x_stride=logT + 1, bits_stride=logT + 1,
                                          want_report=want_report)
         return rep
+
+    def ring_inv_or_zero(self, x, num=None, out=None, x_stride=1, num_stride=1, out_stride=1, want_report=True):
+        """The slotwise inverse-or-zero of ring elements (rs_ring_inv_or_zero): x^-1 where a slot is non-zero, 0 where it is
+        zero; with `num`, num * x^-1.  x: a tensor whose element e is the ring element at x_stride * e ring elements
+        (x_stride = 1: [count][L][N]); likewise num and out (out = None: a new [count][L][N]).  The three may be views of
+        one assignment as long as no x or num row is an output row; num may be x.
+        Returns (out, InvReport), or (out, None) with want_report=False: enqueued only, nothing is downloaded."""
+        assert x_stride >= 1 and num_stride >= 1 and out_stride >= 1, "strides must be at least 1"
+        count = (self._count(x, self.ring_words) - 1) // x_stride + 1 if x.numel() else 0
+        if num is not None and count:
+            assert self._count(num, self.ring_words) >= (count - 1) * num_stride + 1, "num holds fewer than (count - 1) * num_stride + 1 ring elements"
+        if out is None:
+            assert out_stride == 1, "a strided output needs `out`"
+            out = self.ring_empty(count)
+        elif count:
+            assert self._count(out, self.ring_words) >= (count - 1) * out_stride + 1, "out holds fewer than (count - 1) * out_stride + 1 ring elements"
+        rep = _lib.InvReport()
+        _lib.check(self.lib.rs_ring_inv_or_zero(self.h, _ptr(x), x_stride, _ptr(num), num_stride, count, _ptr(out), out_stride,
+                                                C.byref(rep) if want_report else None, self.stream()))
+        if not want_report:
+            return out, None
+        return out, InvReport(*[int(getattr(rep, k)) for k, _ in _lib.InvReport._fields_])
+
+    def is_zero_fill(self, assignment, count, want_report=True):
+        """Fills the inv rows of an is_zero_r1cs assignment [1 + 3 count][L][N] in place from its x rows (block p: rows
+        x, inv, z after the row of `one`): one strided rs_ring_inv_or_zero, x_stride = out_stride = 3.  Returns the report."""
+        rows = assignment.view(-1, self.L, self.N)
+        assert rows.shape[0] == 1 + 3 * count, "not an assignment of %d is-zero blocks" % count
+        _, rep = self.ring_inv_or_zero(rows[1:2 + 3 * (count - 1)], out=rows[2:], x_stride=3, out_stride=3, want_report=want_report)
+        return rep
+
+    def division_fill(self, assignment, count, want_report=True):
+        """Fills the binv and y rows of a division_r1cs assignment [1 + 4 count][L][N] in place from its a and b rows (block
+        p: rows a, b, binv, y after the row of `one`): two strided rs_ring_inv_or_zero of stride 4, binv from b, then y from
+        b with num = a.  Returns the two reports."""
+        rows = assignment.view(-1, self.L, self.N)
+        assert rows.shape[0] == 1 + 4 * count, "not an assignment of %d division blocks" % count
+        last = 4 * (count - 1)
+        b = rows[2:3 + last]
+        _, rep_binv = self.ring_inv_or_zero(b, out=rows[3:], x_stride=4, out_stride=4, want_report=want_report)
+        _, rep_y = self.ring_inv_or_zero(b, num=rows[1:2 + last], out=rows[4:], x_stride=4, num_stride=4, out_stride=4, want_report=want_report)
+        return rep_binv, rep_y
 
     def _require_satisfied(self, dcs, assignment, report=None):
         r = self.r1cs_check(dcs, assignment) if report is None else report

@@ -9,6 +9,7 @@ reduced per RNS limb as uint64[L][nnz] (a signed literal c < 0 is -c's negation 
 constraint of benchmarks/bench_ntt_SEAL.cpp:46-53 multiplies variables by powers of a polynomial), kept
 once in `poly_table` [n_poly][L][N] and referenced per non-zero by `poly_idx` (-1 = the scalar).
 """
+import collections
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -503,6 +504,120 @@ def plaintext_check_assignment(cs_or_logT, xs, q: List[int], constants: bool = F
     blocks = asg[first:].reshape((count, logT + 1) + xs.shape[1:])
     blocks[:, :logT] = bits
     blocks[:, logT] = xs
+    return asg
+
+
+class InvReport(collections.namedtuple("InvReport", "n_zero zero_elem zero_limb zero_slot n_bad bad_elem bad_limb bad_slot bad_x bad_num")):
+    """What an inverse-or-zero reports (rs_inv_report of ringsnark_amd/inverse.h, field for field).  Zeros are ordinary
+    input; clean: no word that is not a canonical residue."""
+    __slots__ = ()
+
+    @property
+    def clean(self):
+        return self.n_bad == 0
+
+
+def inv_or_zero(x, q: List[int], num=None):
+    """The host mirror of rs_ring_inv_or_zero (ringsnark_amd/inverse.h), exact (Python integers).  x: uint64 [count][L][N]
+    (or one element [L][N]); num: None or the same shape.  Per position (element, limb i, slot): 0 < x < q_i gives
+    x^-1 mod q_i, times num when given; x == 0 gives 0 and counts in n_zero; x >= q_i, or num >= q_i, gives 0 and counts
+    in n_bad and not in n_zero.  The firsts are the lowest element, then the lowest limb*N + slot.
+    Returns (out of x's shape, InvReport)."""
+    x = np.asarray(x, dtype=np.uint64)
+    single = x.ndim == 2
+    xs = x[None] if single else x
+    assert xs.ndim == 3 and xs.shape[1] == len(q), xs.shape
+    ns = None
+    if num is not None:
+        ns = np.asarray(num, dtype=np.uint64)
+        ns = ns[None] if single else ns
+        assert ns.shape == xs.shape, (ns.shape, xs.shape)
+    count, L, N = xs.shape
+    out = np.zeros_like(xs)
+    qs = np.array([int(p) for p in q], dtype=np.uint64).reshape(1, L, 1)
+    bad = xs >= qs
+    if ns is not None:
+        bad |= ns >= qs
+    zero = ~bad & (xs == 0)
+    for e, l, s in zip(*np.nonzero(~bad & ~zero)):
+        p = int(q[l])
+        v = pow(int(xs[e, l, s]), p - 2, p)
+        out[e, l, s] = v if ns is None else v * int(ns[e, l, s]) % p
+    fields = [int(zero.sum()), 0, 0, 0, int(bad.sum()), 0, 0, 0, 0, 0]
+    if fields[0]:
+        e, idx = divmod(int(np.argmax(zero.reshape(-1))), L * N)
+        fields[1:4] = [e, idx // N, idx % N]
+    if fields[4]:
+        e, idx = divmod(int(np.argmax(bad.reshape(-1))), L * N)
+        limb, slot = divmod(idx, N)
+        fields[5:10] = [e, limb, slot, int(xs[e, limb, slot]), 0 if ns is None else int(ns[e, limb, slot])]
+    return (out[0] if single else out), InvReport(*fields)
+
+
+def is_zero_r1cs(q: List[int], count: int = 1) -> R1CS:
+    """The is-zero gadget, `count` times.  Variable 1 is the public wire `one` (n_inputs = 1; plaintext_check_r1cs says why
+    a public wire and not the constant); block p is x_p, inv_p, z_p (variables 2 + 3p .. 4 + 3p, 1-based):
+        constraint 2p:      x_p * inv_p = one - z_p
+        constraint 2p + 1:  x_p * z_p   = 0
+    so z_p is 1 in the slots where x_p is zero and 0 elsewhere, and inv_p is the inverse-or-zero of x_p.  With one, x_p
+    and inv_p given the solver finds z_p through the c side of constraint 2p."""
+    assert count >= 1
+    rows = {"a": [], "b": [], "c": []}
+    for p in range(count):
+        x, inv, z = 2 + 3 * p, 3 + 3 * p, 4 + 3 * p
+        rows["a"] += [[(x, 1)], [(x, 1)]]
+        rows["b"] += [[(inv, 1)], [(z, 1)]]
+        rows["c"] += [[(1, 1), (z, -1)], []]
+    return from_rows(2 * count, 1 + 3 * count, 1, rows, q)
+
+
+def is_zero_assignment(xs, q: List[int]) -> np.ndarray:
+    """The host assignment [1 + 3 count][L][N] of is_zero_r1cs from the values xs [count][L][N] (canonical residues): `one`,
+    then per block x, its inverse-or-zero and the zero indicator."""
+    xs = np.asarray(xs, dtype=np.uint64)
+    assert xs.ndim == 3 and xs.shape[1] == len(q), xs.shape
+    inv, rep = inv_or_zero(xs, q)
+    assert rep.clean, "x holds a word that is not a canonical residue"
+    asg = np.empty((1 + 3 * xs.shape[0],) + xs.shape[1:], dtype=np.uint64)
+    asg[0] = 1
+    blocks = asg[1:].reshape((xs.shape[0], 3) + xs.shape[1:])
+    blocks[:, 0] = xs
+    blocks[:, 1] = inv
+    blocks[:, 2] = xs == 0
+    return asg
+
+
+def division_r1cs(q: List[int], count: int = 1) -> R1CS:
+    """Slotwise division, `count` times.  Variable 1 is the public wire `one`; block p is a_p, b_p, binv_p, y_p (variables
+    2 + 4p .. 5 + 4p, 1-based):
+        constraint 2p:      b_p * binv_p = one     (b_p is invertible in every slot)
+        constraint 2p + 1:  y_p * b_p    = a_p"""
+    assert count >= 1
+    rows = {"a": [], "b": [], "c": []}
+    for p in range(count):
+        a, b, binv, y = 2 + 4 * p, 3 + 4 * p, 4 + 4 * p, 5 + 4 * p
+        rows["a"] += [[(b, 1)], [(y, 1)]]
+        rows["b"] += [[(binv, 1)], [(b, 1)]]
+        rows["c"] += [[(1, 1)], [(a, 1)]]
+    return from_rows(2 * count, 1 + 4 * count, 1, rows, q)
+
+
+def division_assignment(a, b, q: List[int]) -> np.ndarray:
+    """The host assignment [1 + 4 count][L][N] of division_r1cs from a, b [count][L][N] (canonical residues): `one`, then
+    per block a, b, the inverse-or-zero of b and the quotient a / b (0 where b is zero: such a slot violates constraint
+    2p)."""
+    a, b = np.asarray(a, dtype=np.uint64), np.asarray(b, dtype=np.uint64)
+    assert a.shape == b.shape and b.ndim == 3 and b.shape[1] == len(q), (a.shape, b.shape)
+    binv, rep = inv_or_zero(b, q)
+    y, rep_y = inv_or_zero(b, q, num=a)
+    assert rep.clean and rep_y.clean, "a or b holds a word that is not a canonical residue"
+    asg = np.empty((1 + 4 * b.shape[0],) + b.shape[1:], dtype=np.uint64)
+    asg[0] = 1
+    blocks = asg[1:].reshape((b.shape[0], 4) + b.shape[1:])
+    blocks[:, 0] = a
+    blocks[:, 1] = b
+    blocks[:, 2] = binv
+    blocks[:, 3] = y
     return asg
 
 
