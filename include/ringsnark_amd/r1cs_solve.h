@@ -12,7 +12,8 @@
  * non-zero modulo every q_l.  It then determines, per limb and slot,
  *     w = (<a,(1,x)> * <b,(1,x)> - <c,(1,x)> without w) * k^-1        (a canonical residue).
  * Nothing else is solved: unknowns on the a / b side (inverse and division witnesses), polynomial coefficients on the
- * target -- such wires stay unsolved and are REPORTED.  The arithmetic is exact: every order of evaluation gives the same
+ * target -- such wires stay unsolved and are REPORTED (bit, inverse and quotient wires as declared hints of a plan: the
+ * entry points of solve_hints.h).  The arithmetic is exact: every order of evaluation gives the same
  * words.
  *
  * The schedule (host, once per system and mask, O(nnz)): given wires have level 0; a step's level is 1 + the highest

@@ -16,6 +16,7 @@ RS_MOD_PLAIN, RS_MOD_COEFF = 0, 1
 RS_KIND_POLY, RS_KIND_ONE = 0, 2
 RS_EVAL_FULL, RS_EVAL_IO, RS_EVAL_MID = 0, 1, 2
 RS_SOLVE_AUTO, RS_SOLVE_LEVELS, RS_SOLVE_WALK = 0, 1, 2
+RS_HINT_BITS, RS_HINT_INV, RS_HINT_QUOT = 1, 2, 3
 
 u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
@@ -65,6 +66,26 @@ class SolveInfo(C.Structure):
 
 class SolveStats(C.Structure):
     _fields_ = [("level_launches", C.c_uint32), ("walk_launches", C.c_uint32)]
+
+
+class SolveHint(C.Structure):  # rs_solve_hint: 0-based variables
+    _fields_ = [("kind", C.c_uint32), ("src", C.c_uint32), ("num", C.c_uint32), ("dst", C.c_uint32), ("nbits", C.c_uint32),
+                ("dst_stride", C.c_uint32)]
+
+
+class HintInfo(C.Structure):
+    _fields_ = [("solve", SolveInfo), ("n_steps", C.c_uint64), ("n_hints_run", C.c_uint64), ("n_hints_blocked", C.c_uint64),
+                ("first_blocked_hint", C.c_uint64)]
+
+
+class HintStats(C.Structure):
+    _fields_ = [("level_launches", C.c_uint32), ("walk_launches", C.c_uint32), ("hint_launches", C.c_uint32)]
+
+
+class HintReport(C.Structure):
+    _fields_ = [("n_bits_bad", C.c_uint64), ("bad_hint", C.c_uint32), ("bad_limb", C.c_uint32), ("bad_slot", C.c_uint32),
+                ("reserved0", C.c_uint32), ("n_zero", C.c_uint64), ("zero_hint", C.c_uint32), ("zero_limb", C.c_uint32),
+                ("zero_slot", C.c_uint32), ("reserved1", C.c_uint32)]
 
 
 class VerifyReport(C.Structure):
@@ -198,6 +219,13 @@ SOLVE_SIGNATURES = {  # every function of include/ringsnark_amd/r1cs_solve.h
     "rs_r1cs_solve": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(SolveStats), vp]),
 }
 
+HINT_SIGNATURES = {  # every function of include/ringsnark_amd/solve_hints.h
+    "rs_r1cs_hint_plan_create": (C.c_int, [vp, vp, u8p, C.POINTER(SolveHint), C.c_size_t, C.POINTER(vp), C.POINTER(HintInfo)]),
+    "rs_r1cs_hint_plan_steps": (C.c_int, [vp, u8p, u32p, u32p, u64p]),
+    "rs_r1cs_hint_plan_destroy": (None, [vp]),
+    "rs_r1cs_solve_hinted": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(HintStats), C.POINTER(HintReport), vp]),
+}
+
 VERIFY_SIGNATURES = {  # every function of include/ringsnark_amd/verify.h
     "rs_io_eval_at": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "rs_groth16_vk_create": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
@@ -296,7 +324,7 @@ def load():
     for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES, **CHECK_SIGNATURES, **SOLVE_SIGNATURES, **VERIFY_SIGNATURES,
                               **KEYGEN_SIGNATURES, **SEEDED_SIGNATURES, **BATCH_SIGNATURES, **MODSWITCH_SIGNATURES, **BITS_SIGNATURES,
                               **VERIFY_BATCH_SIGNATURES, **PACKED_SIGNATURES, **R1CS_BATCH_SIGNATURES,
-                              **INVERSE_SIGNATURES}.items():
+                              **INVERSE_SIGNATURES, **HINT_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -14,8 +14,8 @@
 #include <algorithm>
 
 #include "../../include/ringsnark_amd/r1cs_solve.h"
+#include "r1cs_solve_dev.hpp"
 #include "r1cs_solve_plan.hpp"
-#include "witness_eval.hpp"
 
 namespace rs {
 
@@ -25,56 +25,6 @@ namespace rs {
 constexpr size_t SOLVE_FILL_WORKGROUPS = 256;
 // steps per workgroup of the level kernel: as many as leave the device a few waves of workgroups (as CHECK's rows per workgroup)
 constexpr size_t SOLVE_STEPS_PER_WG = 8;
-
-// the three matrices as the kernels read them
-template <class T>
-struct SolveCsr {
-  const uint32_t *rp[3], *col[3];
-  const T *cf[3];  // [L][nnz]
-  size_t nnz[3];
-  const int32_t *px[3];
-  const T *ptab;
-};
-
-// bounds of the three rows of one step, its target and k^-1: everything of a step that does not depend on the assignment
-template <class T>
-struct SolveStep {
-  uint32_t e0[3], e1[3], wire;
-  T kinv;
-};
-template <class T>
-__device__ __forceinline__ SolveStep<T> load_step(const SolveCsr<T> &cs, const uint32_t *__restrict__ step_row,
-                                                  const uint32_t *__restrict__ step_wire, const T *__restrict__ kinv_limb, size_t s) {
-  SolveStep<T> st;
-  const uint32_t row = step_row[s];
-#pragma unroll
-  for (int w = 0; w < 3; w++) {
-    st.e0[w] = cs.rp[w][row];
-    st.e1[w] = cs.rp[w][row + 1];
-  }
-  st.wire = step_wire[s];
-  st.kinv = kinv_limb[s];
-  return st;
-}
-
-// target = (<a,z> * <b,z> - <c,z> without the target) * k^-1 for one slot pair, stored as canonical residues
-template <class M>
-__device__ __forceinline__ void solve_step(const SolveCsr<typename ArithOf<M>::T> &cs, const SolveStep<typename ArithOf<M>::T> &st,
-                                           uint64_t *asg, size_t S, size_t pair, int limb, const M mod) {
-  using T = typename ArithOf<M>::T;
-  T a0, a1, b0, b1, c0, c1;
-  eval_row_pair_skip<M>(cs.col[0], cs.cf[0] + (size_t)limb * cs.nnz[0], st.e0[0], st.e1[0], asg, S, pair, ~0u, mod, a0, a1, cs.px[0], cs.ptab);
-  eval_row_pair_skip<M>(cs.col[1], cs.cf[1] + (size_t)limb * cs.nnz[1], st.e0[1], st.e1[1], asg, S, pair, ~0u, mod, b0, b1, cs.px[1], cs.ptab);
-  eval_row_pair_skip<M>(cs.col[2], cs.cf[2] + (size_t)limb * cs.nnz[2], st.e0[2], st.e1[2], asg, S, pair, st.wire + 1, mod, c0, c1, cs.px[2], cs.ptab);
-  // two canonical residues, one operand centred (the dyadic product of rs_core.hip); the difference is reduced before it
-  // meets the constant: |product| <= 0.75 p and c < p leave 1.75 p, beyond what mulmod takes beside |k^-1| <= p / 2 at 50 bits
-  const T d0 = reduce(subm(mulmod_dd(a0, center(b0, mod), mod), c0, mod), mod);
-  const T d1 = reduce(subm(mulmod_dd(a1, center(b1, mod), mod), c1, mod), mod);
-  ulonglong2 o;
-  o.x = to_res(canon(mulmod(d0, st.kinv, mod), mod));
-  o.y = to_res(canon(mulmod(d1, st.kinv, mod), mod));
-  reinterpret_cast<ulonglong2 *>(asg + (size_t)st.wire * S)[pair] = o;
-}
 
 // grid: (slot chunks of 256 slot pairs) x (groups of `spw` steps of the level [s_lo, s_hi)), one dimension, ordered by
 // xcd_position.  A thread owns one slot pair.  The rows read (levels below) and the rows written (this level) are disjoint.
@@ -119,8 +69,11 @@ solve_walk_kernel(const SolveCsr<typename ArithOf<M>::T> cs, const uint32_t *__r
   }
 }
 
-// The schedule of r1cs_solve.h.  k: the coefficient sum of every step, [n_steps][L] canonical.
-static void build_schedule(const rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *h_given, rs_r1cs_solve_plan *P, std::vector<uint64_t> &k) {
+// The schedule of r1cs_solve.h, and with hints that of solve_hints.h (r1cs_solve_plan.hpp).  One body: a hint adds reserved
+// wires, which no constraint step may take, and steps of its own, which become ready through a counter of unknown sources as
+// a constraint does through its counters.
+void build_schedule(const rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *h_given, rs_r1cs_solve_plan *P, std::vector<uint64_t> &k,
+                    const rs_solve_hint *hints, size_t n_hints, HintSchedule *hs) {
   const size_t m = cs->m, nv = cs->n_vars;
   const int L = ctx->L;
   RS_REQUIRE(m < ((size_t)1 << 31) && nv < 0xFFFFFFFFull, "constraint system too large for the solver");
@@ -156,6 +109,36 @@ static void build_schedule(const rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *
   }
   auto candidate = [&](size_t j) { return cnt_ab[j] == 0 && cnt_c[j] == 1; };
   std::vector<uint32_t> cand, next, fresh, claimed(nv, 0);
+  // hints: the reserved wires, the unknown sources of every hint, and the wire -> hint adjacency of the sources
+  auto targets = [&](size_t h) { return hints[h].kind == RS_HINT_BITS ? (size_t)hints[h].nbits : (size_t)1; };
+  auto stride = [&](size_t h) { return hints[h].kind == RS_HINT_BITS ? (size_t)hints[h].dst_stride : (size_t)1; };
+  std::vector<uint8_t> reserved, hint_done;
+  std::vector<uint32_t> hcnt, hcand, hnext, hadj_ptr, hadj;
+  if (n_hints) {
+    reserved.assign(nv, 0);
+    hint_done.assign(n_hints, 0);
+    hcnt.assign(n_hints, 0);
+    hadj_ptr.assign(nv + 1, 0);
+    std::vector<std::pair<uint32_t, uint32_t>> occ;  // (wire, hint)
+    for (size_t h = 0; h < n_hints; h++) {
+      for (size_t t = 0; t < targets(h); t++) reserved[hints[h].dst + t * stride(h)] = 1;
+      const uint32_t srcs[2] = {hints[h].src, hints[h].num};
+      const int n_src = hints[h].kind == RS_HINT_QUOT && hints[h].num != hints[h].src ? 2 : 1;
+      for (int i = 0; i < n_src; i++)
+        if (!known[srcs[i]]) {
+          hcnt[h]++;
+          occ.emplace_back(srcs[i], (uint32_t)h);
+          hadj_ptr[srcs[i] + 1]++;
+        }
+      if (hcnt[h] == 0) hcand.push_back((uint32_t)h);
+    }
+    for (size_t v = 0; v < nv; v++) hadj_ptr[v + 1] += hadj_ptr[v];
+    hadj.resize(occ.size());
+    std::vector<uint32_t> fill(hadj_ptr.begin(), hadj_ptr.end() - 1);
+    for (const auto &o : occ) hadj[fill[o.first]++] = o.second;
+    hs->kinds.clear();
+    hs->n_wires = hs->n_run = 0;
+  }
   std::vector<uint8_t> is_step(m, 0);
   std::vector<uint64_t> ksum(L);
   for (size_t j = 0; j < m; j++)
@@ -164,7 +147,8 @@ static void build_schedule(const rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *
   P->wires.clear();
   P->level_ptr.assign(1, 0);
   k.clear();
-  for (uint32_t level = 1; !cand.empty(); level++) {
+  size_t n_constraint_steps = 0;
+  for (uint32_t level = 1; !cand.empty() || !hcand.empty(); level++) {
     std::sort(cand.begin(), cand.end());  // a constraint becomes a candidate once: no duplicates
     fresh.clear();
     for (const uint32_t j : cand) {
@@ -173,6 +157,7 @@ static void build_schedule(const rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *
       for (uint32_t i = c_ptr[j]; i < c_ptr[j + 1]; i++)
         if (!known[c_list[i]]) t = c_list[i];
       if (claimed[t] == level) continue;  // a lower constraint of this level determines it
+      if (n_hints && reserved[t]) continue;  // its hint determines it, or nothing does
       bool poly = false;
       std::fill(ksum.begin(), ksum.end(), 0);
       const size_t z = cs->nnz[2];
@@ -189,9 +174,25 @@ static void build_schedule(const rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *
       k.insert(k.end(), ksum.begin(), ksum.end());
       fresh.push_back(t);
     }
+    n_constraint_steps += fresh.size();
+    const size_t level_lo = P->rows.size() - fresh.size();
+    if (n_hints) {
+      hs->kinds.resize(P->rows.size(), 0);
+      std::sort(hcand.begin(), hcand.end());  // a hint becomes ready once: no duplicates
+      for (const uint32_t h : hcand) {
+        hint_done[h] = 1;
+        hs->n_run++;
+        P->rows.push_back(h);
+        P->wires.push_back(hints[h].dst);
+        k.insert(k.end(), (size_t)L, 1);
+        hs->kinds.push_back(1);
+        for (size_t t = 0; t < targets(h); t++) fresh.push_back((uint32_t)(hints[h].dst + t * stride(h)));
+      }
+      hcand.clear();
+    }
     if (fresh.empty()) break;
     P->level_ptr.push_back(P->rows.size());
-    info.max_width = std::max<uint64_t>(info.max_width, fresh.size());
+    info.max_width = std::max<uint64_t>(info.max_width, P->rows.size() - level_lo);
     next.clear();
     for (const uint32_t t : fresh) known[t] = 1;
     for (const uint32_t t : fresh)
@@ -200,12 +201,23 @@ static void build_schedule(const rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *
         (adj[i] & 1u ? cnt_c : cnt_ab)[j]--;
         if (candidate(j)) next.push_back(j);
       }
+    if (n_hints)
+      for (const uint32_t t : fresh)
+        for (uint32_t i = hadj_ptr[t]; i < hadj_ptr[t + 1]; i++)
+          if (--hcnt[hadj[i]] == 0) hcand.push_back(hadj[i]);
     cand.swap(next);
   }
-  info.n_solved = P->rows.size();
+  info.n_solved = n_constraint_steps;
+  if (n_hints) {
+    for (size_t h = 0; h < n_hints; h++)
+      if (hint_done[h]) info.n_solved += targets(h);
+    hs->n_wires = info.n_solved;
+    hs->n_blocked = n_hints - hs->n_run;
+    hs->first_blocked = std::find(hint_done.begin(), hint_done.end(), 0) - hint_done.begin();
+  }
   info.n_unsolved = nv - info.n_given - info.n_solved;
   info.n_levels = P->level_ptr.size() - 1;
-  info.n_unused = m - info.n_solved;
+  info.n_unused = m - n_constraint_steps;
   info.first_unsolved = nv;
   for (size_t v = 0; v < nv; v++)
     if (!known[v]) {
@@ -234,13 +246,14 @@ static void build_schedule(const rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *
     if (cnt_c[j] == 1 && cnt_ab[j] == 1 && in_ab == t) info.blocked_reason = 5;
     else if (cnt_ab[j] > 0) info.blocked_reason = 1;
     else if (cnt_c[j] > 1) info.blocked_reason = 2;
+    else if (n_hints && reserved[t]) info.blocked_reason = 6;
     else info.blocked_reason = poly ? 3 : 4;
   }
 }
 
 // algorithmic bytes of the steps [s_lo, s_hi): the distinct wires read or written times S * 8, plus the CSR entries and the
 // schedule words touched; FP64 instructions per lane: a modular multiply-add per entry, the product and k^-1 per step
-static void launch_cost(const rs_ctx *ctx, const rs_r1cs_solve_plan *P, std::vector<uint32_t> &seen, uint32_t token, SolveLaunch &ln) {
+void launch_cost(const rs_ctx *ctx, const rs_r1cs_solve_plan *P, std::vector<uint32_t> &seen, uint32_t token, SolveLaunch &ln) {
   const rs_r1cs *cs = P->cs;
   double wires = 0, entries = 0;
   for (size_t s = ln.s_lo; s < ln.s_hi; s++) {
@@ -279,7 +292,7 @@ static void build_launches(const rs_ctx *ctx, rs_r1cs_solve_plan *P) {
 }
 
 template <class M>
-static void solve_run(rs_ctx *ctx, const rs_r1cs_solve_plan *P, uint64_t *d_asg, const std::vector<SolveLaunch> &launches, hipStream_t st) {
+static void solve_launch_arith(rs_ctx *ctx, const rs_r1cs_solve_plan *P, uint64_t *d_asg, const SolveLaunch &ln, hipStream_t st) {
   using T = typename ArithOf<M>::T;
   const rs_r1cs *cs = P->cs;
   SolveCsr<T> k;
@@ -293,22 +306,24 @@ static void solve_run(rs_ctx *ctx, const rs_r1cs_solve_plan *P, uint64_t *d_asg,
   k.ptab = reinterpret_cast<const T *>(cs->d_ptab);
   const T *kinv = reinterpret_cast<const T *>(P->d_kinv);
   const size_t n_steps = P->rows.size(), chunks = (ctx->ring_words() / 2 + 255) / 256;
-  for (const SolveLaunch &ln : launches) {
-    if (ln.kind == 0) {
-      size_t spw = SOLVE_STEPS_PER_WG;
-      while (spw > 1 && chunks * ((ln.s_hi - ln.s_lo + spw - 1) / spw) < 4096) spw >>= 1;
-      const size_t groups = (ln.s_hi - ln.s_lo + spw - 1) / spw;
-      RS_REQUIRE(chunks * groups < ((size_t)1 << 31), "level too wide for one launch of the solver");
-      ProfScope p(ctx, st, "solve_level", ln.bytes, ln.ops);
-      hipLaunchKernelGGL(solve_level_kernel<M>, dim3((unsigned)(chunks * groups)), dim3(256), 0, st, k, P->d_rows, P->d_wires, kinv, n_steps,
-                         ln.s_lo, ln.s_hi, d_asg, ctx->N, ctx->L, CtxArith<M>::qmod(ctx), (unsigned)groups, (unsigned)spw);
-    } else {
-      ProfScope p(ctx, st, "solve_walk", ln.bytes, ln.ops);
-      hipLaunchKernelGGL(solve_walk_kernel<M>, dim3((unsigned)chunks), dim3(256), 0, st, k, P->d_rows, P->d_wires, kinv, n_steps, ln.s_lo,
-                         ln.s_hi, d_asg, ctx->N, ctx->L, CtxArith<M>::qmod(ctx));
-    }
-    RS_HIP(hipGetLastError());
+  if (ln.kind == 0) {
+    size_t spw = SOLVE_STEPS_PER_WG;
+    while (spw > 1 && chunks * ((ln.s_hi - ln.s_lo + spw - 1) / spw) < 4096) spw >>= 1;
+    const size_t groups = (ln.s_hi - ln.s_lo + spw - 1) / spw;
+    RS_REQUIRE(chunks * groups < ((size_t)1 << 31), "level too wide for one launch of the solver");
+    ProfScope p(ctx, st, "solve_level", ln.bytes, ln.ops);
+    hipLaunchKernelGGL(solve_level_kernel<M>, dim3((unsigned)(chunks * groups)), dim3(256), 0, st, k, P->d_rows, P->d_wires, kinv, n_steps,
+                       ln.s_lo, ln.s_hi, d_asg, ctx->N, ctx->L, CtxArith<M>::qmod(ctx), (unsigned)groups, (unsigned)spw);
+  } else {
+    ProfScope p(ctx, st, "solve_walk", ln.bytes, ln.ops);
+    hipLaunchKernelGGL(solve_walk_kernel<M>, dim3((unsigned)chunks), dim3(256), 0, st, k, P->d_rows, P->d_wires, kinv, n_steps, ln.s_lo,
+                       ln.s_hi, d_asg, ctx->N, ctx->L, CtxArith<M>::qmod(ctx));
   }
+  RS_HIP(hipGetLastError());
+}
+
+void solve_launch(rs_ctx *ctx, const rs_r1cs_solve_plan *P, uint64_t *d_asg, const SolveLaunch &ln, hipStream_t st) {
+  dispatch_arith(ctx, [&](auto tag) { solve_launch_arith<decltype(tag)>(ctx, P, d_asg, ln, st); });
 }
 
 template <class M>
@@ -318,6 +333,29 @@ static uint64_t konst_bits(uint64_t v, uint64_t p) {
   static_assert(sizeof(c) == sizeof(w), "constants of both arithmetics travel as 64-bit words");
   std::memcpy(&w, &c, sizeof(w));
   return w;
+}
+
+void upload_schedule(const rs_ctx *ctx, rs_r1cs_solve_plan *P, const std::vector<uint64_t> &k, const uint8_t *kinds, size_t n_index) {
+  const rs_r1cs *cs = P->cs;
+  // everything that indexes memory on the device, checked before any launch can use it
+  const size_t n = P->rows.size(), L = (size_t)ctx->L;
+  RS_REQUIRE(P->wires.size() == n && k.size() == n * L && P->level_ptr.front() == 0 && P->level_ptr.back() == n, "inconsistent schedule");
+  for (size_t s = 0; s < n; s++)
+    RS_REQUIRE(P->rows[s] < (kinds && kinds[s] ? n_index : cs->m) && P->wires[s] < cs->n_vars, "schedule index out of range");
+  for (size_t l = 0; l + 1 < P->level_ptr.size(); l++) RS_REQUIRE(P->level_ptr[l] < P->level_ptr[l + 1], "level pointers are not monotone");
+  if (!n) return;
+  std::vector<uint64_t> kinv(L * n);
+  for (size_t s = 0; s < n; s++)
+    for (size_t l = 0; l < L; l++) {
+      const uint64_t inv = host::invmod(k[s * L + l], ctx->q[l]);
+      kinv[l * n + s] = ctx->use_int ? konst_bits<ModI>(inv, ctx->q[l]) : konst_bits<Mod>(inv, ctx->q[l]);
+    }
+  RS_HIP(hipMalloc(&P->d_rows, sizeof(uint32_t) * n));
+  RS_HIP(hipMalloc(&P->d_wires, sizeof(uint32_t) * n));
+  RS_HIP(hipMalloc(&P->d_kinv, sizeof(uint64_t) * L * n));
+  RS_HIP(hipMemcpy(P->d_rows, P->rows.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+  RS_HIP(hipMemcpy(P->d_wires, P->wires.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+  RS_HIP(hipMemcpy(P->d_kinv, kinv.data(), sizeof(uint64_t) * L * n, hipMemcpyHostToDevice));
 }
 
 }  // namespace rs
@@ -339,25 +377,7 @@ int rs_r1cs_solve_plan_create(rs_ctx *ctx, const rs_r1cs *cs, const uint8_t *h_g
   P->cs = cs;
   std::vector<uint64_t> k;
   build_schedule(ctx, cs, h_given, P, k);
-  // everything that indexes memory on the device, checked before any launch can use it
-  const size_t n = P->rows.size(), L = (size_t)ctx->L;
-  RS_REQUIRE(P->wires.size() == n && P->level_ptr.front() == 0 && P->level_ptr.back() == n, "inconsistent schedule");
-  for (size_t s = 0; s < n; s++) RS_REQUIRE(P->rows[s] < cs->m && P->wires[s] < cs->n_vars, "schedule index out of range");
-  for (size_t l = 0; l + 1 < P->level_ptr.size(); l++) RS_REQUIRE(P->level_ptr[l] < P->level_ptr[l + 1], "level pointers are not monotone");
-  if (n) {
-    std::vector<uint64_t> kinv(L * n);
-    for (size_t s = 0; s < n; s++)
-      for (size_t l = 0; l < L; l++) {
-        const uint64_t inv = host::invmod(k[s * L + l], ctx->q[l]);
-        kinv[l * n + s] = ctx->use_int ? konst_bits<ModI>(inv, ctx->q[l]) : konst_bits<Mod>(inv, ctx->q[l]);
-      }
-    RS_HIP(hipMalloc(&P->d_rows, sizeof(uint32_t) * n));
-    RS_HIP(hipMalloc(&P->d_wires, sizeof(uint32_t) * n));
-    RS_HIP(hipMalloc(&P->d_kinv, sizeof(uint64_t) * L * n));
-    RS_HIP(hipMemcpy(P->d_rows, P->rows.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-    RS_HIP(hipMemcpy(P->d_wires, P->wires.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-    RS_HIP(hipMemcpy(P->d_kinv, kinv.data(), sizeof(uint64_t) * L * n, hipMemcpyHostToDevice));
-  }
+  upload_schedule(ctx, P, k);
   build_launches(ctx, P);
   if (h_info) *h_info = P->info;
   holder.p = nullptr;
@@ -394,7 +414,7 @@ int rs_r1cs_solve(rs_ctx *ctx, const rs_r1cs_solve_plan *plan, uint64_t *d_assig
   if (!launches.empty()) {
     std::unique_lock<std::mutex> lk(ctx->mu, std::defer_lock);
     if (ctx->profiling) lk.lock();  // the record ProfScope appends to belongs to the holder of mu
-    dispatch_arith(ctx, [&](auto tag) { solve_run<decltype(tag)>(ctx, plan, d_assignment, launches, S(stream)); });
+    for (const SolveLaunch &ln : launches) solve_launch(ctx, plan, d_assignment, ln, S(stream));
   }
   if (h_stats) *h_stats = stats;
   RS_API_END

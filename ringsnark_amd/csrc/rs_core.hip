@@ -671,7 +671,7 @@ using namespace rs;
 extern "C" {
 
 const char *rs_last_error(void) { return g_last_error.c_str(); }
-int rs_version(void) { return 113; }  // 113: inverse.h (rs_ring_inv_or_zero: slotwise inverse-or-zero and quotient wires, in place in an assignment); 112: r1cs_batch.h (a batch of assignments solved and checked in one pass over the system); 111: packed.h (bit-packed seeded proving keys); 110: verify_batch.h (a batch of proofs against one verification key, one verdict each); 109: bits.h (rs_ring_bit_decompose: bit rows of ring elements, in place in an assignment); 108: modswitch.h (mod-switched proofs: switch, level decode, level wire format, level verifiers); 107: r1cs_solve.h (assignment solver); 106: batch.h (batched provers; up to 33 groups in rs_msm); 105: seeded.h (seeded proving keys); 104: keygen.h (generators); 103: verify.h (rs_io_eval_at, verifiers); 102: rs_r1cs_check; 101: rs_msm_vec::slot_const (struct must be zero-initialised), rs_enc_noise_budget, RS_ERR_NOISE
+int rs_version(void) { return 114; }  // 113: inverse.h (rs_ring_inv_or_zero: slotwise inverse-or-zero and quotient wires, in place in an assignment); 112: r1cs_batch.h (a batch of assignments solved and checked in one pass over the system); 111: packed.h (bit-packed seeded proving keys); 110: verify_batch.h (a batch of proofs against one verification key, one verdict each); 109: bits.h (rs_ring_bit_decompose: bit rows of ring elements, in place in an assignment); 108: modswitch.h (mod-switched proofs: switch, level decode, level wire format, level verifiers); 107: r1cs_solve.h (assignment solver); 106: batch.h (batched provers; up to 33 groups in rs_msm); 105: seeded.h (seeded proving keys); 104: keygen.h (generators); 103: verify.h (rs_io_eval_at, verifiers); 102: rs_r1cs_check; 101: rs_msm_vec::slot_const (struct must be zero-initialised), rs_enc_noise_budget, RS_ERR_NOISE
 
 int rs_ctx_create(int device, int N, int L, const uint64_t *q, int N_enc, int K, const uint64_t *Q, rs_ctx **out) {
   RS_API_BEGIN

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from .params import RingParams
-from .r1cs import R1CS, SOLVE_BLOCKED, InvReport, R1csCheck, SolveInfo, given_mask, plaintext_check_layout
+from .r1cs import R1CS, SOLVE_BLOCKED, HintReport, HintSolveInfo, InvReport, R1csCheck, SolveInfo, given_mask, plaintext_check_layout
 
 
 def to_device(a: np.ndarray, device) -> torch.Tensor:
@@ -126,6 +126,45 @@ class SolvePlan:
     def close(self):
         if getattr(self, "h", None) and self.dev.lib is not None:
             self.dev.lib.rs_r1cs_solve_plan_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+
+HintSolveStats = collections.namedtuple("HintSolveStats", "level_launches walk_launches hint_launches")
+
+
+class HintPlan:
+    """A solve plan with hints on the device (rs_r1cs_hint_plan of ringsnark_amd/solve_hints.h): the schedule that completes an
+    assignment of `dcs` from the given wires and the declared hints (ringsnark_amd.r1cs.Hint).  .info is a HintSolveInfo;
+    close() (or garbage collection) frees it.  Keeps `dcs` alive: the plan reads its matrices."""
+
+    def __init__(self, dev, dcs, given, hints):
+        self.dev, self.dcs, self.hints = dev, dcs, list(hints)
+        mask = given_mask(dcs.cs, given)
+        arr = (_lib.SolveHint * max(len(self.hints), 1))(*[_lib.SolveHint(h.kind, h.src, h.num, h.dst, h.nbits, h.dst_stride)
+                                                          for h in self.hints])
+        h, info = C.c_void_p(), _lib.HintInfo()
+        _lib.check(dev.lib.rs_r1cs_hint_plan_create(dev.h, dcs.h, mask.ctypes.data_as(_lib.u8p), arr if self.hints else None,
+                                                    len(self.hints), C.byref(h), C.byref(info)))
+        self.h = h
+        self.info = HintSolveInfo(*[int(getattr(info.solve, k)) for k, _ in _lib.SolveInfo._fields_], int(info.n_steps),
+                                  int(info.n_hints_run), int(info.n_hints_blocked), int(info.first_blocked_hint))
+
+    def steps(self):
+        """([(kind, index, wire)] in the order they run -- kind 0: constraint and target, kind 1: hint and its first target --,
+        level_ptr [n_levels + 1])"""
+        n = self.info.n_steps
+        kind = np.zeros(max(n, 1), dtype=np.uint8)
+        index, wire = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        lp = np.zeros(self.info.n_levels + 1, dtype=np.uint64)
+        _lib.check(self.dev.lib.rs_r1cs_hint_plan_steps(self.h, kind.ctypes.data_as(_lib.u8p), index.ctypes.data_as(_lib.u32p),
+                                                        wire.ctypes.data_as(_lib.u32p), lp.ctypes.data_as(_lib.u64p)))
+        return [(int(k), int(i), int(w)) for k, i, w in zip(kind[:n], index[:n], wire[:n])], [int(x) for x in lp]
+
+    def close(self):
+        if getattr(self, "h", None) and self.dev.lib is not None:
+            self.dev.lib.rs_r1cs_hint_plan_destroy(self.h)
         self.h = None
 
     __del__ = close
@@ -797,6 +836,33 @@ class Device:
         stats = _lib.SolveStats()
         _lib.check(self.lib.rs_r1cs_solve_batch(self.h, plan.h, B, ptrs, SOLVE_MODES[mode], C.byref(stats), self.stream()))
         return SolveStats(int(stats.level_launches), int(stats.walk_launches))
+
+    def r1cs_hint_plan(self, dcs, given, hints):
+        """The schedule that completes an assignment of `dcs` from the `given` wires and the declared `hints` (a list of
+        ringsnark_amd.r1cs.Hint): rs_r1cs_hint_plan_create.  A plan with unsolved wires or blocked hints is still a plan;
+        .info says what is missing and why.  A hint the library refuses raises RsError."""
+        return HintPlan(self, dcs, given, hints)
+
+    def r1cs_solve_hinted(self, plan, assignment, mode="auto", allow_partial=False, want_report=True):
+        """Fills the rows of the wires that the constraints and the hints of `plan` determine in `assignment` [n_vars][L][N]
+        in place (rs_r1cs_solve_hinted).  Returns (HintSolveStats, HintReport), or (HintSolveStats, None) with
+        want_report=False: enqueued only, nothing is downloaded.  Bad bits and zero sources are answers in the report, not
+        errors.  With unsolved wires it raises ValueError unless allow_partial, as r1cs_solve does."""
+        assert self._count(assignment, self.ring_words) == plan.dcs.n_vars, "the solver addresses every row of the assignment"
+        i = plan.info
+        if i.n_unsolved and not allow_partial:
+            raise ValueError("the given wires and the hints do not determine the assignment: %d of %d variables unsolved, first unsolved "
+                             "variable %d; first blocked constraint %d: %s; %d hints never ready" % (
+                                 i.n_unsolved, plan.dcs.n_vars, i.first_unsolved, i.first_blocked, SOLVE_BLOCKED[i.blocked_reason],
+                                 i.n_hints_blocked))
+        stats, rep = _lib.HintStats(), _lib.HintReport()
+        _lib.check(self.lib.rs_r1cs_solve_hinted(self.h, plan.h, _ptr(assignment), SOLVE_MODES[mode], C.byref(stats),
+                                                 C.byref(rep) if want_report else None, self.stream()))
+        stats = HintSolveStats(int(stats.level_launches), int(stats.walk_launches), int(stats.hint_launches))
+        if not want_report:
+            return stats, None
+        return stats, HintReport(int(rep.n_bits_bad), int(rep.bad_hint), int(rep.bad_limb), int(rep.bad_slot), int(rep.n_zero),
+                                 int(rep.zero_hint), int(rep.zero_limb), int(rep.zero_slot))
 
     def r1cs_check_batch(self, dcs, assignments, want_flags=False):
         """r1cs_check for B FULL assignments (1 <= B <= 8; members may alias) in one pass over the three matrices

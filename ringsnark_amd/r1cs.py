@@ -10,6 +10,7 @@ constraint of benchmarks/bench_ntt_SEAL.cpp:46-53 multiplies variables by powers
 once in `poly_table` [n_poly][L][N] and referenced per non-zero by `poly_idx` (-1 = the scalar).
 """
 import collections
+import dataclasses
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -153,8 +154,95 @@ def solve_schedule(cs: R1CS, given, q: List[int]):
     sum is non-zero modulo every q_l.  Given wires have level 0, a step's level is 1 + the highest level among the wires
     its constraint reads, a wire is determined in the lowest level in which a constraint for it is ready and there by the
     lowest such constraint; steps are ordered by (level, constraint).  Unknown-counters per constraint and a wire ->
-    constraint adjacency: O(nnz) apart from sorting each level.
+    constraint adjacency: O(nnz) apart from sorting each level.  One scheduler body: solve_hinted_schedule without hints.
     Returns (steps [(constraint, variable)], level_ptr [n_levels + 1], SolveInfo)."""
+    steps, level_ptr, info = solve_hinted_schedule(cs, given, (), q)
+    return [(j, t) for _, j, t in steps], level_ptr, SolveInfo(*[getattr(info, f.name) for f in dataclasses.fields(SolveInfo)])
+
+
+RS_HINT_BITS, RS_HINT_INV, RS_HINT_QUOT = 1, 2, 3
+SOLVE_BLOCKED[6] = "the only unknown is reserved for a hint that never became ready"
+
+
+@dataclass(frozen=True)
+class Hint:
+    """A declared hint (rs_solve_hint of ringsnark_amd/solve_hints.h, field for field; 0-based variables).
+    BITS: variable dst + k * dst_stride <- bit k of src, k < nbits.  INV: dst <- src^-1, 0 where src is 0.
+    QUOT: dst <- num * src^-1, 0 where src is 0."""
+    kind: int
+    src: int
+    num: int
+    dst: int
+    nbits: int = 0
+    dst_stride: int = 1
+
+    @staticmethod
+    def bits(src, dst, nbits, dst_stride=1):
+        return Hint(RS_HINT_BITS, src, 0, dst, nbits, dst_stride)
+
+    @staticmethod
+    def inv(src, dst):
+        return Hint(RS_HINT_INV, src, 0, dst)
+
+    @staticmethod
+    def quot(num, src, dst):
+        return Hint(RS_HINT_QUOT, src, num, dst)
+
+    @property
+    def targets(self):
+        return [self.dst + k * self.dst_stride for k in range(self.nbits)] if self.kind == RS_HINT_BITS else [self.dst]
+
+    @property
+    def sources(self):
+        return [self.src, self.num] if self.kind == RS_HINT_QUOT and self.num != self.src else [self.src]
+
+
+@dataclass
+class HintSolveInfo(SolveInfo):
+    """What a hint plan reports (rs_r1cs_hint_info of ringsnark_amd/solve_hints.h): the fields of SolveInfo -- n_solved counts
+    wires, from constraints and hints alike; max_width counts the steps of a level -- and those of the hints."""
+    n_steps: int = 0
+    n_hints_run: int = 0
+    n_hints_blocked: int = 0
+    first_blocked_hint: int = 0  # lowest hint that never became ready; the number of hints when there is none
+
+
+def check_hints(cs: R1CS, given, hints, q: List[int]):
+    """The refusals of rs_r1cs_hint_plan_create (ValueError), in its order."""
+    known = given_mask(cs, given).astype(bool)
+    nv, taken = cs.n_vars, set()
+    for i, h in enumerate(hints):
+        if h.kind not in (RS_HINT_BITS, RS_HINT_INV, RS_HINT_QUOT):
+            raise ValueError("hint %d: unknown kind" % i)
+        if not (0 <= h.src < nv and 0 <= h.dst < nv and (h.kind != RS_HINT_QUOT or 0 <= h.num < nv)):
+            raise ValueError("hint %d: variable out of range" % i)
+        if h.kind == RS_HINT_BITS:
+            if not 1 <= h.nbits <= max_nbits(q):
+                raise ValueError("hint %d: nbits must be between 1 and min_i floor(log2 q_i) = %d" % (i, max_nbits(q)))
+            if h.dst_stride < 1:
+                raise ValueError("hint %d: dst_stride must be at least 1" % i)
+            if h.dst + (h.nbits - 1) * h.dst_stride >= nv:
+                raise ValueError("hint %d: variable out of range" % i)
+        for v in h.targets:
+            if known[v]:
+                raise ValueError("hint %d: target %d is given" % (i, v))
+            if v in taken:
+                raise ValueError("hint %d: target %d is named twice" % (i, v))
+            if v in h.sources:
+                raise ValueError("hint %d: a source is among its own targets" % i)
+            taken.add(v)
+
+
+def solve_hinted_schedule(cs: R1CS, given, hints, q: List[int]):
+    """The schedule of the solver with hints (ringsnark_amd/solve_hints.h), the host mirror of rs_r1cs_hint_plan_create: the
+    rules of solve_schedule, and: the targets of every hint are reserved (no constraint step determines one; for the constraint
+    counters they are unknown until their hint has run); a hint is ready when its sources are known, its level is 1 + the
+    highest level of its sources; steps are ordered by level, then constraint steps by row, then hint steps by hint index.
+    Hints that never become ready (a cycle across hints, an unknown source) are reported, not refused.
+    Returns (steps [(kind, index, wire)] -- kind 0: constraint and target, kind 1: hint and its first target --,
+    level_ptr [n_levels + 1], HintSolveInfo)."""
+    hints = list(hints)
+    check_hints(cs, given, hints, q)
     m, nv = cs.m, cs.n_vars
     known = given_mask(cs, given).astype(bool)
     n_given = int(known.sum())
@@ -170,19 +258,27 @@ def solve_schedule(cs: R1CS, given, q: List[int]):
                 if v >= 0 and not known[v] and v not in side:
                     side.add(v)
                     adj[v].append((j, n == "c"))
+    reserved = {v for h in hints for v in h.targets}
+    unk_h = [{v for v in h.sources if not known[v]} for h in hints]
+    hadj = collections.defaultdict(list)  # wire -> hints that read it
+    for i, srcs in enumerate(unk_h):
+        for v in srcs:
+            hadj[v].append(i)
+    hint_done = [False] * len(hints)
     candidate = lambda j: not unk_ab[j] and len(unk_c[j]) == 1
     pidx = None if cs.poly_idx is None else cs.poly_idx["c"]
     coeff = cs.mats["c"][2]
-    steps, level_ptr, is_step, max_width = [], [0], [False] * m, 0
+    steps, level_ptr, is_step, max_width, n_wires = [], [0], [False] * m, 0, 0
     cand = [j for j in range(m) if candidate(j)]
-    while cand:
-        fresh = {}
+    hcand = [i for i, srcs in enumerate(unk_h) if not srcs]
+    while cand or hcand:
+        fresh, width = {}, len(steps)
         for j in sorted(cand):
             if not candidate(j):
                 continue
             (t,) = unk_c[j]
-            if t in fresh:
-                continue  # a lower constraint of this level determines it
+            if t in fresh or t in reserved:
+                continue  # a lower constraint of this level determines it; its hint determines it, or nothing does
             on_t = [e for e in range(rp["c"][j], rp["c"][j + 1]) if col["c"][e] == t + 1]
             if pidx is not None and any(pidx[e] >= 0 for e in on_t):
                 continue
@@ -190,12 +286,18 @@ def solve_schedule(cs: R1CS, given, q: List[int]):
                 continue
             fresh[t] = j
             is_step[j] = True
-            steps.append((j, t))
+            steps.append((0, j, t))
+        for i in sorted(hcand):
+            hint_done[i] = True
+            steps.append((1, i, hints[i].dst))
+            for v in hints[i].targets:
+                fresh[v] = None
         if not fresh:
             break
         level_ptr.append(len(steps))
-        max_width = max(max_width, len(fresh))
-        cand = []
+        max_width = max(max_width, len(steps) - width)
+        n_wires += len(fresh)
+        cand, hcand = [], []
         for t in fresh:
             known[t] = True
         for t in fresh:
@@ -203,6 +305,10 @@ def solve_schedule(cs: R1CS, given, q: List[int]):
                 (unk_c if in_c else unk_ab)[j].discard(t)
                 if candidate(j):
                     cand.append(j)
+            for i in hadj[t]:
+                unk_h[i].discard(t)
+                if not unk_h[i]:
+                    hcand.append(i)
     unsolved = [v for v in range(nv) if not known[v]]
     blocked = [j for j in range(m) if not is_step[j] and (unk_ab[j] or unk_c[j])]
     reason = 0
@@ -217,23 +323,18 @@ def solve_schedule(cs: R1CS, given, q: List[int]):
         else:
             (t,) = unk_c[j]
             poly = pidx is not None and any(pidx[e] >= 0 for e in range(rp["c"][j], rp["c"][j + 1]) if col["c"][e] == t + 1)
-            reason = 3 if poly else 4
-    info = SolveInfo(n_given, len(steps), len(unsolved), unsolved[0] if unsolved else nv, len(level_ptr) - 1, max_width,
-                     m - len(steps), blocked[0] if blocked else m, reason)
+            reason = 6 if t in reserved else 3 if poly else 4
+    n_constraint = sum(1 for s in steps if s[0] == 0)
+    n_run = sum(hint_done)
+    info = HintSolveInfo(n_given, n_wires, len(unsolved), unsolved[0] if unsolved else nv, len(level_ptr) - 1, max_width,
+                         m - n_constraint, blocked[0] if blocked else m, reason, len(steps), n_run, len(hints) - n_run,
+                         hint_done.index(False) if n_run < len(hints) else len(hints))
     return steps, level_ptr, info
 
 
-def solve(cs: R1CS, given, assignment, q: List[int]) -> np.ndarray:
-    """The assignment solver on the host in exact Python integers, the host mirror of rs_r1cs_solve: a copy of `assignment`
-    [n_vars][L][N] with the rows of the solved wires filled in,
-        w = (<a,(1,x)> * <b,(1,x)> - <c,(1,x)> without w) * k^-1   per limb and slot, canonical.
-    Reads given and already solved rows only; rows of unsolved wires are returned as they were."""
-    out = np.array(assignment, dtype=np.uint64)
-    L = len(q)
-    assert out.ndim == 3 and out.shape[0] == cs.n_vars and out.shape[1] == L, out.shape
-    steps, _, _ = solve_schedule(cs, given, q)
-
-    def row(name, j, l, skip):
+def _solve_step(cs: R1CS, out, j, t, q):
+    """Row t of `out` from constraint j: (<a,(1,x)> * <b,(1,x)> - <c,(1,x)> without t) * k^-1, exact."""
+    def row(name, l, skip):
         rp, col, coeff = cs.mats[name]
         pidx = None if cs.poly_idx is None else cs.poly_idx[name]
         acc, k = np.zeros(out.shape[2], dtype=object), 0
@@ -245,12 +346,120 @@ def solve(cs: R1CS, given, assignment, q: List[int]) -> np.ndarray:
             acc = (acc + cf * (1 if col[e] == 0 else out[int(col[e]) - 1, l].astype(object))) % int(q[l])
         return acc, k
 
-    for j, t in steps:
-        for l in range(L):
-            p = int(q[l])
-            (a, _), (b, _), (c, k) = row("a", j, l, -1), row("b", j, l, -1), row("c", j, l, t + 1)
-            out[t, l] = ((a * b - c) * pow(k % p, -1, p) % p).astype(np.uint64)
+    for l in range(len(q)):
+        p = int(q[l])
+        (a, _), (b, _), (c, k) = row("a", l, -1), row("b", l, -1), row("c", l, t + 1)
+        out[t, l] = ((a * b - c) * pow(k % p, -1, p) % p).astype(np.uint64)
+
+
+def solve(cs: R1CS, given, assignment, q: List[int]) -> np.ndarray:
+    """The assignment solver on the host in exact Python integers, the host mirror of rs_r1cs_solve: a copy of `assignment`
+    [n_vars][L][N] with the rows of the solved wires filled in,
+        w = (<a,(1,x)> * <b,(1,x)> - <c,(1,x)> without w) * k^-1   per limb and slot, canonical.
+    Reads given and already solved rows only; rows of unsolved wires are returned as they were."""
+    out = np.array(assignment, dtype=np.uint64)
+    assert out.ndim == 3 and out.shape[0] == cs.n_vars and out.shape[1] == len(q), out.shape
+    for j, t in solve_schedule(cs, given, q)[0]:
+        _solve_step(cs, out, j, t, q)
     return out
+
+
+class HintReport(collections.namedtuple("HintReport", "n_bits_bad bad_hint bad_limb bad_slot n_zero zero_hint zero_limb zero_slot")):
+    """What a hinted solve reports (rs_solve_hint_report of ringsnark_amd/solve_hints.h): bad positions (hint, limb, slot) of
+    BITS hints and zero source positions of INV and QUOT hints, with the first of each: lowest hint, then lowest
+    limb*N + slot; zeros when there is none.  Both are answers, not errors."""
+    __slots__ = ()
+
+    @property
+    def clean(self):
+        return self.n_bits_bad == 0 and self.n_zero == 0
+
+
+def solve_hinted(cs: R1CS, given, hints, assignment, q: List[int]):
+    """The solver with hints on the host in exact Python integers, the host mirror of rs_r1cs_solve_hinted: a copy of
+    `assignment` [n_vars][L][N] with the rows of the solved wires filled in, constraint steps as solve does, hint steps by
+    bit_decompose and inv_or_zero.  Returns (assignment, HintReport)."""
+    hints = list(hints)
+    out = np.array(assignment, dtype=np.uint64)
+    assert out.ndim == 3 and out.shape[0] == cs.n_vars and out.shape[1] == len(q), out.shape
+    n_bad = n_zero = 0
+    first_bad = first_zero = None  # (hint, limb, slot)
+    for kind, i, t in solve_hinted_schedule(cs, given, hints, q)[0]:
+        if kind == 0:
+            _solve_step(cs, out, i, t, q)
+            continue
+        h = hints[i]
+        if h.kind == RS_HINT_BITS:
+            bits, rep = bit_decompose(out[h.src], h.nbits, q)
+            for k, v in enumerate(h.targets):
+                out[v] = bits[k]
+            n_bad += rep.n_bad
+            if rep.n_bad:
+                first_bad = min(first_bad or (i, rep.first_limb, rep.first_slot), (i, rep.first_limb, rep.first_slot))
+        else:
+            out[h.dst], rep = inv_or_zero(out[h.src], q, num=out[h.num] if h.kind == RS_HINT_QUOT else None)
+            assert rep.clean, "a source row holds a word that is not a canonical residue"
+            n_zero += rep.n_zero
+            if rep.n_zero:
+                first_zero = min(first_zero or (i, rep.zero_limb, rep.zero_slot), (i, rep.zero_limb, rep.zero_slot))
+    return out, HintReport(n_bad, *(first_bad or (0, 0, 0)), n_zero, *(first_zero or (0, 0, 0)))
+
+
+def running_max_r1cs(q: List[int], nbits: int, count: int):
+    """The running maximum of x_0 .. x_count by comparisons on nbits-bit differences.  Public wires: `one` (variable 0,
+    0-based), x_0 .. x_count (variables 1 .. count + 1).  Stage j < count has the wires s_j, b_{j,0} .. b_{j,nbits-1}, m_j
+    (variables count + 2 + j (nbits + 2) ..), with m_{-1} = x_0, and the constraints
+        (m_{j-1} - x_{j+1} + 2^(nbits-1) one) * one = s_j
+        b_{j,k} * (one - b_{j,k}) = 0                      once per bit
+        s_j * one = sum_k 2^k b_{j,k}
+        b_{j,nbits-1} * (m_{j-1} - x_{j+1}) = m_j - x_{j+1}
+    and the hint BITS(s_j -> b_j): 3 count levels, which alternate constraint, hint, constraint.  For inputs below
+    2^(nbits-1), m_j = max(x_0 .. x_{j+1}).  Returns (R1CS, [Hint])."""
+    assert nbits >= 2 and count >= 1
+    rows = {"a": [], "b": [], "c": []}
+
+    def add(a, b, c):
+        rows["a"].append(a), rows["b"].append(b), rows["c"].append(c)
+
+    one, hints, prev = 1, [], 2
+    for j in range(count):
+        x = 3 + j
+        s = count + 3 + j * (nbits + 2)
+        b = [s + 1 + k for k in range(nbits)]
+        mx = s + 1 + nbits
+        add([(prev, 1), (x, -1), (one, 1 << (nbits - 1))], [(one, 1)], [(s, 1)])
+        for k in range(nbits):
+            add([(b[k], 1)], [(one, 1), (b[k], -1)], [])
+        add([(s, 1)], [(one, 1)], [(b[k], 1 << k) for k in range(nbits)])
+        add([(b[-1], 1)], [(prev, 1), (x, -1)], [(mx, 1), (x, -1)])
+        hints.append(Hint.bits(s - 1, b[0] - 1, nbits))
+        prev = mx
+    return from_rows(count * (nbits + 3), count + 2 + count * (nbits + 2), count + 2, rows, q), hints
+
+
+def running_max_layout(nbits: int, count: int):
+    """0-based variables of running_max_r1cs: (s_j, first bit of stage j, m_j) for every stage."""
+    return [(count + 2 + j * (nbits + 2), count + 3 + j * (nbits + 2), count + 3 + j * (nbits + 2) + nbits) for j in range(count)]
+
+
+def continued_fraction_r1cs(q: List[int], count: int):
+    """y_{j+1} = c_j / (y_j + d_j), `count` times.  Public wires: `one` (variable 0, 0-based), y_0 (1), then c_j, d_j
+    (2 + 2j, 3 + 2j).  Stage j has the wires t_j, y_{j+1} (variables 2 + 2 count + 2j ..) and the constraints
+        (y_j + d_j) * one = t_j,      y_{j+1} * t_j = c_j
+    and the hint QUOT(c_j, t_j -> y_{j+1}): 2 count levels, all slot-local.  Where t_j is zero y_{j+1} is 0, and the second
+    constraint holds only if c_j is zero there too.  Returns (R1CS, [Hint])."""
+    assert count >= 1
+    rows = {"a": [], "b": [], "c": []}
+    one, hints, y = 1, [], 2
+    for j in range(count):
+        c, d = 3 + 2 * j, 4 + 2 * j
+        t = 3 + 2 * count + 2 * j
+        rows["a"] += [[(y, 1), (d, 1)], [(t + 1, 1)]]
+        rows["b"] += [[(one, 1)], [(t, 1)]]
+        rows["c"] += [[(t, 1)], [(c, 1)]]
+        hints.append(Hint.quot(c - 1, t - 1, t))
+        y = t + 1
+    return from_rows(2 * count, 2 + 4 * count, 2 + 2 * count, rows, q), hints
 
 
 def chain_r1cs(m: int, q: List[int]) -> R1CS:
